@@ -11,6 +11,10 @@ N GPUs: one process per GPU (launched by torch.distributed.run, or by this scrip
 without a launcher).  c2/c5: each rank registers its own pairs (replicas, weak scaling).  c4: a fixed
 set of 4096 pairs sharded contiguously over the ranks (strong scaling).  Per-registration result records are gathered
 once at the end (xchu_slam_amd/batch.py; RCCL over xGMI when the group is nccl).
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints one JSON line; `--full`
+adds the CPU baseline legs (cpu_baseline, vs_cpu), which run after the timed steps.  `--dump-outputs DIR` writes what
+the timed path returned in its last timed step as DIR/<name>.npy (seeded inputs: comparable between builds).
 """
 from __future__ import annotations
 
@@ -55,6 +59,33 @@ WORKLOADS = {
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs DIR: what the timed path returned to its caller in the last timed step, one DIR/<name>.npy per
+    array (float32 kept, everything else as float64).  The inputs are seeded, so two builds run with the same arguments
+    can be compared array by array."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"wrote {', '.join(sorted(out))} ({total} bytes) to {out_dir}")
+
+
+def result_arrays(res: dict) -> dict:
+    """One registration's result as its caller receives it (NdtResult): the final transform and the scalar fields."""
+    return {"final_tf": np.asarray(res["final_tf"], np.float32),
+            "result": np.array([res[k] for k in ("nr_iterations", "converged", "trans_probability", "score", "n_passes",
+                                                 "n_pairs", "solver_fallbacks")], np.float64)}
 
 
 def make_pool(rank: int, n_pairs: int, wl: dict):
@@ -290,7 +321,14 @@ def run_c3(args, wl):
         "ape_m": {"mean": round(float(np.mean(ape)), 4), "max": round(float(np.max(ape)), 4), "final": round(ape[-1], 4)},
         "cpu_baseline": None,
     }
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        # every scan's record of the replay call (the last scan's is the last row); timings left out
+        dump_outputs(args.dump_outputs, {
+            "t_localizer": np.stack([r["t_localizer"] for r in recs]).astype(np.float32),
+            "scan_records": np.array([[r[k] for k in ("fitness_score", "has_converged", "final_num_iteration", "keyframe",
+                                                      "localmap_reset", "n_localmap", "n_passes", "n_pairs")] for r in recs],
+                                     np.float64)})
+    if args.cpu_baseline:
         try:
             line["cpu_baseline"] = cpu_baseline_c3(scans[:n_scans], args.cpu_budget, wl["resolution"])
             line["vs_cpu"] = round(value / line["cpu_baseline"]["value"], 2)
@@ -336,7 +374,11 @@ def run_fe(args, wl):
             "dtype": "f32 (f64 distance sums)", "data": "synthetic raw scans (tests/helpers.raw_scan)",
             "config": {"workload": wl["desc"], "n_raw": wl["n_raw"], "mean_filtered_points": round(float(np.mean(outs)), 1)},
             "cpu_baseline": None}
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        pts = np.empty((outs[-1], 4), np.float32)  # the last step's /filtered_points cloud (x, y, z, intensity)
+        _lib.check(lib.ndt_memcpy_d2h(ndt.ctx, pts.ctypes.data_as(C.c_void_p), d_out, pts.nbytes), ndt.ctx)
+        dump_outputs(args.dump_outputs, {"filtered_points": pts})
+    if args.cpu_baseline:
         import oracle_lib
         t0 = time.perf_counter()
         k = 0
@@ -598,7 +640,9 @@ def run_replicas(args, wl, dd: Dist):
         "mean_translation_error_m": round(float(np.mean(errs)), 4) if errs else None,
         "cpu_baseline": None,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, result_arrays(results[-1]))  # rank 0's last timed registration
+    if world == 1 and args.cpu_baseline:
         try:
             p = pool[0]
             line["cpu_baseline"] = cpu_baseline(p.target, p.source, p.guess, args.cpu_budget, wl["resolution"])
@@ -792,7 +836,10 @@ def run_c4(args, wl, dd: Dist, backend_factory=None):
         "max_translation_error_m": round(float(err_stats[1]), 4),
         "cpu_baseline": None,
     }
-    if dd.world == 1 and not args.no_cpu_baseline and mine and hasattr(backend, "host_pair"):
+    if args.dump_outputs:
+        # the gathered table of every pair's record (batch.result_record; the last pair's is the last row)
+        dump_outputs(args.dump_outputs, {"records": table})
+    if dd.world == 1 and args.cpu_baseline and mine and hasattr(backend, "host_pair"):
         try:
             t, s, g = backend.host_pair(mine[0])
             line["cpu_baseline"] = cpu_baseline(t, s, g, args.cpu_budget, wl["resolution"])
@@ -811,14 +858,22 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=0, help="c2/c5: distinct scan/localmap pairs per rank (cycled); 0 = default")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-budget", type=float, default=40.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also time the CPU baseline (the oracle on the same workload: cpu_baseline, "
+                         "vs_cpu); a plain run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--cpu-budget", type=float, default=40.0, help="with --full: seconds of wall time for the CPU baseline")
     ap.add_argument("--save-traj", default="", help="c3: write the per-scan trajectory / timings (.npz)")
     ap.add_argument("--records-out", default="", help="c4: rank 0 saves the gathered per-pair result table (.npy)")
     ap.add_argument("--no-kernel-stamps", action="store_true", help="time without the in-kernel pass stamps (no roofline timing)")
     argv = sys.argv[1:] if argv is None else argv
     args = ap.parse_args(argv)
     args.steps_given = any(a == "--steps" or a.startswith("--steps=") for a in argv)
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     return args, argv
 
 

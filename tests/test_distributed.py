@@ -73,7 +73,7 @@ def test_gloo_world2_matches_single_process():
     assert np.array_equal(got[0], single)          # bit-identical per pair for shard count 1 vs 2
 
 
-def _run_bench_host(tmp_path, gpus):
+def _run_bench_host(tmp_path, gpus, extra=()):
     """bench.py --workload c4 through its own launcher (gpus > 1: bench.spawn_ranks) with the host aligner."""
     import json
     import subprocess
@@ -82,7 +82,8 @@ def _run_bench_host(tmp_path, gpus):
     script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bench_host_rank.py")
     rec = str(tmp_path / f"rec{gpus}.npy")
     out = tmp_path / f"out{gpus}.txt"
-    argv = ["--gpus", str(gpus), "--workload", "c4", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--records-out", rec]
+    argv = ["--gpus", str(gpus), "--workload", "c4", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--records-out", rec,
+            *extra]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     with open(out, "w") as f:
         if gpus > 1:
@@ -108,3 +109,17 @@ def test_bench_launcher_world2_matches_world1(tmp_path):
     assert two["scaling"] == "strong" and two["config"]["pairs_per_rank"] == [2, 3]
     assert rec1.shape == (5, batch.RECORD_WIDTH) and rec2.shape == rec1.shape
     assert np.array_equal(rec1, rec2)  # bit-identical per pair whatever the shard count
+
+
+def test_bench_dump_outputs_writes_the_timed_results(tmp_path):
+    """--dump-outputs DIR: the records the timed batch returned, as float64 DIR/records.npy; --steps sets the number of
+    timed steps and the line carries ms_per_step; a run without --full measures no CPU baseline."""
+    dump = tmp_path / "dump"
+    line, rec = _run_bench_host(tmp_path, 1, extra=("--dump-outputs", str(dump)))
+    assert sorted(os.listdir(dump)) == ["records.npy"]
+    got = np.load(dump / "records.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, rec)
+    assert line["steps"] == 5 and rec.shape[0] == 5
+    assert line["ms_per_step"] > 0 and line["unit"] == "scans/s" and line["higher_is_better"] is True
+    assert abs(line["value"] * line["ms_per_step"] / 1000.0 - 1.0) < 1e-2  # value = steps / timed seconds
+    assert line["cpu_baseline"] is None and "vs_cpu" not in line

@@ -5,7 +5,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 O=gpurun_out/c4; rm -rf $O; mkdir -p $O
-timeout -k 10 600 python bench.py --workload c4 > $O/c4_4096.json 2> $O/c4_4096.err || { echo "c4 failed"; tail -5 $O/c4_4096.err; exit 1; }
+timeout -k 10 600 python bench.py --workload c4 --full > $O/c4_4096.json 2> $O/c4_4096.err || { echo "c4 failed"; tail -5 $O/c4_4096.err; exit 1; }
 python3 -c "import json; d=json.loads(open('$O/c4_4096.json').read().strip().splitlines()[-1]); print('c4', d['value'], d['roofline'], d.get('cpu_baseline'))"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --workload c4 --steps 256 --warmup 8 --no-cpu-baseline > $O/prof.json 2> $O/prof.err || { echo "rocprof failed"; exit 1; }
 python3 tools/kstats.py $O/prof/run_kernel_stats.csv 256 > $O/rocprof_c4_summary.txt; head -12 $O/rocprof_c4_summary.txt
