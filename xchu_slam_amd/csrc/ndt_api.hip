@@ -554,6 +554,9 @@ constexpr int kRadixWideKeys = 4 << 20;
 int radix_items(const ndt_ctx* c, int n) {
     return ceil_div(n, kTileKeys) < c->n_cu ? 4 : (n >= kRadixWideKeys ? 24 : 16);
 }
+// look-back status words of a sort of nb tiles: [4 passes][nb tiles][256 digits], then the group totals of the two-level
+// look-back, [4 passes][ceil(nb / 16) groups][256] (voxel_build.hip kGroupTiles); the key kernels clear all of them
+size_t radix_status_words(int nb) { return (size_t)4 * 256 * ((size_t)nb + (size_t)ceil_div(nb, 16)); }
 void launch_radix_pass(const ndt_ctx* c, Lane L, int items, int nb, int* k0, int* v0, int* k1, int* v1, int n, int pass,
                        const GridHeader* h, GridHeader* herr, int last_pass = 3) {
     auto* kern = items == 4 ? k_radix_onesweep<4> : items == 16 ? k_radix_onesweep<16> : k_radix_onesweep<24>;
@@ -594,7 +597,7 @@ ndt_status enqueue_bin_and_sort(ndt_ctx* c, Lane L, const float4* pts, int n, in
     const size_t n_kv = cloud_span ? (size_t)n + (size_t)n / 4 : (size_t)n;
     TRY(ensure(c, L.s.k0, n_kv)); TRY(ensure(c, L.s.v0, n_kv)); TRY(ensure(c, L.s.k1, n_kv)); TRY(ensure(c, L.s.v1, n_kv));
     TRY(ensure(c, L.s.radix_aux, kRadixAuxWords));
-    TRY(ensure(c, L.s.radix_status, (size_t)4 * 256 * nb_sort));
+    TRY(ensure(c, L.s.radix_status, radix_status_words(nb_sort)));
     TRY(ensure(c, L.s.seg_start, (size_t)n + 1));
     // min/max partials (and the digit histograms cleared), then keys: every keys workgroup derives the header itself
     hipLaunchKernelGGL(k_minmax, dim3(nb_mm), dim3(kBlock), 0, L.st, pts, n, dense, L.s.mm.p, L.s.radix_aux.p,
@@ -602,7 +605,7 @@ ndt_status enqueue_bin_and_sort(ndt_ctx* c, Lane L, const float4* pts, int n, in
     const int nb_keys = std::max(1, std::min(ceil_div(n, 4 * kBlock), 512));
     hipLaunchKernelGGL(k_keys, dim3(nb_keys), dim3(kBlock), 0, L.st, pts, n, dense, L.s.mm.p, nb_mm, h, leaf, c->prm.min_points_per_voxel,
                        c->prm.min_covar_eigvalue_mult, layout, binning, L.s.k0.p, L.s.v0.p, L.s.radix_aux.p, L.s.radix_status.p,
-                       4 * 256 * nb_sort, cloud_span ? c->grid.p : nullptr, (long long)c->grid.cap, cloud_span ? c->table.p : nullptr,
+                       (int)radix_status_words(nb_sort), cloud_span ? c->grid.p : nullptr, (long long)c->grid.cap, cloud_span ? c->table.p : nullptr,
                        1LL << c->max_log2cap, nullptr, 0);
     for (int pass = 0; pass < passes; ++pass)
         launch_radix_pass(c, L, items, nb_sort, L.s.k0.p, L.s.v0.p, L.s.k1.p, L.s.v1.p, n, pass, h, h, passes - 1);
@@ -706,7 +709,7 @@ ndt_status enqueue_target_append(ndt_ctx* c, int n_old, int n_new, const float4*
     const int nb_sort = std::max(1, ceil_div(nq, kBlock * items));
     TRY(ensure(c, Q.s.k0, nq)); TRY(ensure(c, Q.s.v0, nq)); TRY(ensure(c, Q.s.k1, nq)); TRY(ensure(c, Q.s.v1, nq));
     TRY(ensure(c, Q.s.radix_aux, kRadixAuxWords));
-    TRY(ensure(c, Q.s.radix_status, (size_t)4 * 256 * nb_sort));
+    TRY(ensure(c, Q.s.radix_status, radix_status_words(nb_sort)));
     TRY(ensure(c, c->s.seg_start, (size_t)M + 1));
     hipLaunchKernelGGL(k_minmax, dim3(nb_mm), dim3(kBlock), 0, c->stream, pts_new, n_new, 1, Q.s.mm.p, Q.s.radix_aux.p, c->d_clk + 3,
                        c->d_hdr, c->d_hdr_prev, copy_to);
@@ -718,7 +721,7 @@ ndt_status enqueue_target_append(ndt_ctx* c, int n_old, int n_new, const float4*
     const int nb_keys = std::max(1, (int)std::min<long long>(std::max<long long>(ceil_div(nq, 4 * kBlock), ceil_div(clear_words, 4LL * kBlock)), 512));
     hipLaunchKernelGGL(k_keys, dim3(nb_keys), dim3(kBlock), 0, c->stream, pts_new, n_new, 1, Q.s.mm.p, nb_mm, c->d_hdr, c->prm.resolution,
                        c->prm.min_points_per_voxel, c->prm.min_covar_eigvalue_mult, 0, 0, Q.s.k0.p, Q.s.v0.p, Q.s.radix_aux.p,
-                       Q.s.radix_status.p, 4 * 256 * nb_sort, c->grid.p, (long long)c->grid.cap, c->table.p, 1LL << c->max_log2cap,
+                       Q.s.radix_status.p, (int)radix_status_words(nb_sort), c->grid.p, (long long)c->grid.cap, c->table.p, 1LL << c->max_log2cap,
                        c->d_hdr_prev, n_old);
     const int passes = radix_launch_passes(c);
     for (int pass = 0; pass < passes; ++pass)
@@ -1235,13 +1238,13 @@ ndt_status enqueue_source_order(ndt_ctx* c, const float T[16]) {
     const int items = radix_items(c, n);
     const int nb_sort = std::max(1, ceil_div(n, kBlock * items));
     TRY(ensure(c, c->s.radix_aux, kRadixAuxWords));
-    TRY(ensure(c, c->s.radix_status, (size_t)4 * 256 * nb_sort));
+    TRY(ensure(c, c->s.radix_status, radix_status_words(nb_sort)));
     Mat4f Tm;
     std::memcpy(Tm.m, T, sizeof(Tm.m));
     HIPCHK(c, hipMemsetAsync(c->s.radix_aux.p, 0, kRadixAuxWords * sizeof(int), c->stream));
     const int nb_keys = std::max(1, std::min(ceil_div(n, kBlock), 1024));
     hipLaunchKernelGGL(k_src_keys, dim3(nb_keys), dim3(kBlock), 0, c->stream, c->source.p, n, Tm, c->d_hdr, c->ord_k0.p, c->ord_v0.p,
-                       c->s.radix_aux.p, c->s.radix_status.p, 4 * 256 * nb_sort);
+                       c->s.radix_aux.p, c->s.radix_status.p, (int)radix_status_words(nb_sort));
     const int passes = radix_launch_passes(c);
     for (int pass = 0; pass < passes; ++pass)
         launch_radix_pass(c, main_lane(c), items, nb_sort, c->ord_k0.p, c->ord_v0.p, c->ord_k1.p, c->ord_v1.p, n, pass, c->d_hdr, c->d_hdr,

@@ -301,6 +301,65 @@ constexpr unsigned kStCnt = (1u << 30) - 1u;
 // s_sleep, so 2^15 polls bound a stuck tile to ~30 ms against look-backs that resolve in microseconds; at 2^22 each of the
 // four time-outs of C4's 16-queue x 8-stream run waited ~2 s (profiles/r06/c4_queues)
 constexpr int kSpinLimit = 1 << 15;
+// Sorts of at most kTwoLevelTiles tiles (every sort whose tiles can all be resident) resolve the look-back in two levels
+// over groups of kGroupTiles tiles; the group totals sit behind the tiles' words: [4 passes][groups][256] (ndt_api.hip
+// radix_status_words)
+#ifndef NDT_TWOLEVEL_TILES
+#define NDT_TWOLEVEL_TILES 1024
+#endif
+constexpr int kTwoLevelTiles = NDT_TWOLEVEL_TILES, kGroupTiles = 16;
+
+// Profiling build only (-DNDT_SORT_STAMPS, `make VARIANT=sortdbg VFLAGS=-DNDT_SORT_STAMPS`): phase stamps (100 MHz device
+// clock) of the first, the middle and the last tile of each pass, per instantiation, summed over the launches;
+// tools/sort_phases.py reads them.  Row: [0] launches, [1..5] ticks from the tile's start to the end of the key loads /
+// ranking / aggregate store / look-back / scatter, [6] tiles of the last launch, [8..13] the last launch's raw stamps.
+#ifdef NDT_SORT_STAMPS
+constexpr int kSortStampWords = 16;
+__device__ unsigned long long g_sort_ts[3 * 4 * 3 * kSortStampWords];
+#define NDT_SORT_STAMP_BEGIN()                                                                                              \
+    const int sort_cls = tile == 0 ? 0 : tile == nb - 1 ? 2 : tile == nb / 2 ? 1 : -1;                                      \
+    unsigned long long* sort_row =                                                                                          \
+        tid == 0 && sort_cls >= 0 ? &g_sort_ts[(((ITEMS == 4 ? 0 : ITEMS == 16 ? 1 : 2) * 4 + pass) * 3 + sort_cls) * kSortStampWords] \
+                                  : nullptr;                                                                                \
+    const unsigned long long sort_t0 = __builtin_amdgcn_s_memrealtime();                                                    \
+    if (sort_row) { sort_row[0] += 1ull; sort_row[6] = (unsigned long long)nb; sort_row[8] = sort_t0; }
+#define NDT_SORT_STAMP(slot)                                                  \
+    do {                                                                      \
+        __syncthreads();                                                      \
+        if (sort_row) {                                                       \
+            const unsigned long long _n = __builtin_amdgcn_s_memrealtime();   \
+            sort_row[(slot)] += _n - sort_t0;                                 \
+            sort_row[8 + (slot)] = _n;                                        \
+        }                                                                     \
+    } while (0)
+#else
+#define NDT_SORT_STAMP_BEGIN() do { } while (0)
+#define NDT_SORT_STAMP(slot) do { } while (0)
+#endif
+
+// Two-level look-back: N status words of one digit, `stride` words apart (`cnt` <= N of them exist, wave-uniform), every
+// load in flight together; status_take adds their counts once all of them are published.
+template <int N>
+__device__ __forceinline__ void status_load(unsigned (&wd)[N], const unsigned* base, int stride, int cnt, int tid) {
+    // the base stays a scalar the compiler recomputes the N addresses from at every call: hoisted out of the polling
+    // loops they would hold 2 N registers
+    asm volatile("" : "+s"(base));
+#pragma unroll
+    for (int u = 0; u < N; ++u)
+        wd[u] = u < cnt ? __hip_atomic_load(base + (ptrdiff_t)u * stride + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kStAgg;
+}
+template <int N>
+__device__ __forceinline__ bool status_take(const unsigned (&wd)[N], unsigned* sum) {
+    bool all = true;
+    unsigned s = 0;
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        all = all && (wd[u] & ~kStCnt) != 0u;
+        s += wd[u] & kStCnt;
+    }
+    if (all) *sum += s;
+    return all;
+}
 
 // One pass = one kernel.  Tiles (ITEMS * kBlock keys: 4096 for large sorts, 6144 from 4 M keys, 1024 when the sort has fewer tiles
 // than CUs, so that a small sort's per-tile latency is short) are indexed by blockIdx.x (see kScanAgg below for why
@@ -309,8 +368,9 @@ constexpr int kSpinLimit = 1 << 15;
 // consecutive keys of its tile and ranks them stably with no workgroup barrier: item by item (index order), the
 // lanes of one digit find each other with 8 ballots, read the wave's running count of that digit in LDS and the
 // group's first lane advances it.  One barrier later, thread = digit turns the per-wave counts into per-wave
-// offsets and the tile's count, publishes the count (decoupled look-back status), resolves its exclusive prefix by
-// walking back over earlier tiles and adds the global digit base from the histogram of k_keys.  Large tiles are
+// offsets and the tile's count, publishes the count (decoupled look-back status), scans the global digit base from the
+// histogram of k_keys (loaded at the kernel's start) and resolves its exclusive prefix from earlier tiles: in two
+// levels over groups of 16 tiles up to kTwoLevelTiles tiles, by walking back over them in larger sorts.  Large tiles are
 // first placed in digit order in LDS and leave as one contiguous run of stores per digit; small tiles (~4 keys per
 // digit) scatter straight from the ranks.  Output is the same as a hist/scan/scatter pass: bitwise deterministic.
 template <int ITEMS>
@@ -336,14 +396,25 @@ __global__ __launch_bounds__(kBlock) void k_radix_onesweep(int* __restrict__ k0,
     __shared__ int s_tile;
     __shared__ int wcnt[NW][256];   // per-wave running digit counts, then per-wave exclusive offsets
     __shared__ int dpos[256];       // per digit: tile-local start (staged) or global position of the tile's first key
+    __shared__ int gpos[kStage ? 256 : 1];   // staged: per digit, global position minus tile-local start
     __shared__ int lds_scan[NW];
     __shared__ int s_key[kStage ? TILE : 1];
     __shared__ int s_val[kStage ? TILE : 1];
-    if (tid == 0) s_tile = tickets ? atomicAdd(&radix_aux[kRadixCopies * 1024 + pass], 1) : (int)blockIdx.x;
+    // the pass histogram of this digit (k_keys' copies, final before the pass starts): loaded first, summed and scanned
+    // after the aggregate is out, so that neither the loads nor the scan sit behind the look-back
+    int dpart[kRadixCopies];
 #pragma unroll
-    for (int q = 0; q < NW; ++q) wcnt[q][tid] = 0;
-    __syncthreads();
-    const int tile = s_tile;
+    for (int q = 0; q < kRadixCopies; ++q) dpart[q] = radix_aux[q * 1024 + pass * 256 + tid];
+    // default order: tile = blockIdx.x, so the key loads wait for no barrier; a wave clears its own counter row
+    int tile = blockIdx.x;
+    if (tickets) {
+        if (tid == 0) s_tile = atomicAdd(&radix_aux[kRadixCopies * 1024 + pass], 1);
+        __syncthreads();
+        tile = __builtin_amdgcn_readfirstlane(s_tile);   // uniform: tile addresses stay scalar
+    }
+    NDT_SORT_STAMP_BEGIN();
+#pragma unroll
+    for (int q = 0; q < 256 / 64; ++q) wcnt[w][q * 64 + lane] = 0;
     const int base = tile * TILE;
     const int wbase = base + w * (ITEMS * 64);
     int key[ITEMS], val[ITEMS], rk[ITEMS];
@@ -353,6 +424,7 @@ __global__ __launch_bounds__(kBlock) void k_radix_onesweep(int* __restrict__ k0,
         key[r] = i < n ? kin[i] : 0;
         val[r] = i < n ? vin[i] : 0;
     }
+    NDT_SORT_STAMP(1);
     // A: rank among the wave's earlier keys of the same digit (wave-synchronous LDS: a wave's LDS operations complete
     // in order, the fences only keep the compiler from reordering them)
     const unsigned long long lt = (lane == 0) ? 0ull : ((~0ull) >> (64 - lane));
@@ -360,13 +432,19 @@ __global__ __launch_bounds__(kBlock) void k_radix_onesweep(int* __restrict__ k0,
     for (int r = 0; r < ITEMS; ++r) {
         const bool valid = wbase + r * 64 + lane < n;
         const int digit = (key[r] >> shift) & 255;
-        unsigned long long m = __ballot(valid);
+        // lanes of the same digit: per bit one ballot, and per half of the mask one xnor with the lane's own bit spread
+        // over the word (0 or ~0) and one and; the stamps put the ranking at a third of the pass, bound by these
+        // instructions and not by the counter's round trips
+        const unsigned long long mv = __ballot(valid);
+        unsigned mlo = (unsigned)mv, mhi = (unsigned)(mv >> 32);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
-            const bool bit = (digit >> b) & 1;
-            const unsigned long long bb = __ballot(bit);
-            m &= bit ? bb : ~bb;
+            const unsigned e = (unsigned)__builtin_amdgcn_sbfe(key[r], (unsigned)(shift + b), 1u);
+            const unsigned long long bb = __ballot(e != 0u);
+            mlo &= ~((unsigned)bb ^ e);
+            mhi &= ~((unsigned)(bb >> 32) ^ e);
         }
+        const unsigned long long m = ((unsigned long long)mhi << 32) | mlo;
         const int before = wcnt[w][digit];
         const int below = __popcll(m & lt);
         rk[r] = before + below;
@@ -378,6 +456,7 @@ __global__ __launch_bounds__(kBlock) void k_radix_onesweep(int* __restrict__ k0,
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
     }
+    NDT_SORT_STAMP(2);
     __syncthreads();
     // B: thread = digit: per-wave exclusive offsets, the tile's count published at once (later tiles' look-back sums it)
     int agg_i = 0;
@@ -390,10 +469,17 @@ __global__ __launch_bounds__(kBlock) void k_radix_onesweep(int* __restrict__ k0,
     unsigned* st = status + (size_t)pass * nb * 256;
     const unsigned agg = (unsigned)agg_i;
     __hip_atomic_store(&st[(size_t)tile * 256 + tid], (tile == 0 ? kStPre : kStAgg) | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    NDT_SORT_STAMP(3);
+    // global base of this digit = exclusive scan of the pass histogram (its barriers also publish the offsets above)
+    int tot;
+    int dcount = 0;
+#pragma unroll
+    for (int q = 0; q < kRadixCopies; ++q) dcount += dpart[q];
+    const int dbase = block_exclusive_scan(dcount, lds_scan, &tot);
     int lstart = 0;
     if constexpr (kStage) {
         int ltot;
-        lstart = block_exclusive_scan(agg_i, lds_scan, &ltot);  // its barriers also publish the offsets above
+        lstart = block_exclusive_scan(agg_i, lds_scan, &ltot);
         dpos[tid] = lstart;
         __syncthreads();
 #pragma unroll
@@ -408,7 +494,42 @@ __global__ __launch_bounds__(kBlock) void k_radix_onesweep(int* __restrict__ k0,
     // look back over earlier tiles (stops at the first inclusive prefix), publish the inclusive prefix.  Status words
     // are agent-scope atomics: the per-XCD L2s are not coherent.
     unsigned excl = 0;
-    if (tile > 0) {
+    if (nb <= kTwoLevelTiles) {
+        // Two-level look-back (every sort whose tiles can all be resident).  Tiles form groups of kGroupTiles; the last
+        // tile of a group also publishes the group's total (the aggregates of its predecessors in the group plus its
+        // own).  A tile's exclusive prefix = the aggregates of its predecessors in its group (<= 15 words) + the totals
+        // of the groups before it (<= 63 words), loaded a window at a time with every load of a window in flight
+        // together.  Nobody waits for a prefix: aggregates are published without waiting, totals after waiting on
+        // aggregates only, so the waiting depth is two whatever the tile count.
+        const int ng = (nb + kGroupTiles - 1) / kGroupTiles;
+        unsigned* gst = status + ((size_t)4 * nb + (size_t)pass * ng) * 256;
+        const int g = tile / kGroupTiles, p = tile % kGroupTiles;
+        constexpr int GW = kStage ? 32 : 8;    // group totals in flight per thread beside the group's own <= 15 aggregates
+        const unsigned* abase = st + (size_t)tile * 256 - 256;   // predecessor u of the group: abase - 256 u
+        unsigned aw[kGroupTiles - 1], gw[GW];
+        status_load<kGroupTiles - 1>(aw, abase, -256, p, tid);
+        status_load<GW>(gw, gst, 256, g, tid);
+        int spin = 0;
+        bool lost = false;
+        unsigned in_sum = 0, grp_sum = 0;
+        while (!status_take<kGroupTiles - 1>(aw, &in_sum)) {
+            if (++spin > kSpinLimit) { lost = true; break; }
+            __builtin_amdgcn_s_sleep(1);
+            status_load<kGroupTiles - 1>(aw, abase, -256, p, tid);
+        }
+        if (p == kGroupTiles - 1 && !lost)
+            __hip_atomic_store(&gst[(size_t)g * 256 + tid], kStAgg | ((in_sum + agg) & kStCnt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int j0 = 0; j0 < g && !lost; j0 += GW) {
+            if (j0 > 0) status_load<GW>(gw, gst + (size_t)j0 * 256, 256, g - j0, tid);
+            while (!status_take<GW>(gw, &grp_sum)) {
+                if (++spin > kSpinLimit) { lost = true; break; }
+                __builtin_amdgcn_s_sleep(1);
+                status_load<GW>(gw, gst + (size_t)j0 * 256, 256, g - j0, tid);
+            }
+        }
+        if (lost) atomicOr(&herr->pad[0], kBuildErrLookback);  // sort_error
+        excl = in_sum + grp_sum;
+    } else if (tile > 0) {
         // walk back over earlier tiles kLookBack at a time (their status loads in flight together), summing
         // aggregates until the first inclusive prefix; a window stops at the first tile not yet published and is
         // re-read from there
@@ -447,19 +568,14 @@ __global__ __launch_bounds__(kBlock) void k_radix_onesweep(int* __restrict__ k0,
         }
         __hip_atomic_store(&st[(size_t)tile * 256 + tid], kStPre | ((excl + agg) & kStCnt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    // global base of this digit = exclusive scan of the pass histogram
-    int tot;
-    int dcount = 0;
-#pragma unroll
-    for (int q = 0; q < kRadixCopies; ++q) dcount += radix_aux[q * 1024 + pass * 256 + tid];
-    const int dbase = block_exclusive_scan(dcount, lds_scan, &tot);
+    NDT_SORT_STAMP(4);
     if constexpr (kStage) {
-        dpos[tid] = dbase + (int)excl - lstart;
+        gpos[tid] = dbase + (int)excl - lstart;   // not dpos: waves still placing keys read it, no barrier since
         __syncthreads();
         const int m_tile = min(TILE, n - base);
         for (int j = tid; j < m_tile; j += kBlock) {
             const int k = s_key[j];
-            const int pos = dpos[(k >> shift) & 255] + j;
+            const int pos = gpos[(k >> shift) & 255] + j;
             kout[pos] = k;
             vout[pos] = s_val[j];
         }
@@ -475,6 +591,7 @@ __global__ __launch_bounds__(kBlock) void k_radix_onesweep(int* __restrict__ k0,
                 vout[pos] = val[r];
             }
     }
+    NDT_SORT_STAMP(5);
 }
 
 template __global__ void k_radix_onesweep<4>(int*, int*, int*, int*, int, int, const GridHeader*, int*, unsigned*, int, GridHeader*,
@@ -1449,3 +1566,18 @@ __global__ __launch_bounds__(kFitBlock) __attribute__((amdgpu_waves_per_eu(NDT_F
 
 
 }  // namespace ndt
+
+#ifdef NDT_SORT_STAMPS
+// profiling build only: copies the sort's phase stamps to the host (tools/sort_phases.py), optionally clearing them
+extern "C" int ndt_dbg_read_sort(unsigned long long* host, size_t count, int clear) {
+    const size_t n = count < sizeof(ndt::g_sort_ts) / sizeof(unsigned long long) ? count : sizeof(ndt::g_sort_ts) / sizeof(unsigned long long);
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && host) e = hipMemcpyFromSymbol(host, HIP_SYMBOL(ndt::g_sort_ts), n * sizeof(unsigned long long), 0, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && clear) {
+        void* p = nullptr;
+        e = hipGetSymbolAddress(&p, HIP_SYMBOL(ndt::g_sort_ts));
+        if (e == hipSuccess) e = hipMemset(p, 0, sizeof(ndt::g_sort_ts));
+    }
+    return (int)e;
+}
+#endif
