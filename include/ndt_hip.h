@@ -173,6 +173,61 @@ ndt_status ndt_fitness_score_async_aligned(ndt_ctx* ctx, double max_range, const
  * ndt_synchronize. */
 ndt_status ndt_fitness_index_async(ndt_ctx* ctx);
 
+/* ---- Point-to-point ICP: pcl::IterativeClosestPoint<PointXYZI, PointXYZI> as pgo_node's PGO::ICPRefine drives it
+ * (xchu_mapping/src/pgo_node.cpp:404-483) — a second pcl::Registration operator on the same ctx: it aligns the ctx's
+ * current source (setInputSource) to its current target (setInputTarget) and searches the nearest-neighbour index
+ * getFitnessScore uses (cell size = the ctx's resolution).  Semantics (PCL 1.7: CorrespondenceEstimation,
+ * TransformationEstimationSVD, DefaultConvergenceCriteria; parity unpinned): per iteration the nearest target
+ * point of every source point over all target points (FLANN L2_Simple in f32, equal distances to the lowest target
+ * index), pairs with d^2 <= max_corr_dist^2 kept, fewer than 3 pairs = NDT_ICP_NO_CORRESPONDENCES; Umeyama estimate
+ * without scale (f64 sums and SVD where PCL has f32: documented deviation), applied in f32 to the cloud and to the final
+ * transformation; then the criteria in the order of ndt_icp_state, the first that holds ends the align.  These additions
+ * leave every existing layout as it is (NDT_HIP_ABI_VERSION stays 2). */
+typedef enum {
+    NDT_ICP_NOT_CONVERGED = 0,
+    NDT_ICP_ITERATIONS = 1,          /* iterations >= max_iter                                                      */
+    NDT_ICP_TRANSFORM = 2,           /* 0.5 (trace R - 1) >= 1 - trans_eps and |t|^2 <= trans_eps (trans_eps > 0)     */
+    NDT_ICP_ABS_MSE = 3,             /* |mse - previous mse| < 1e-12                                                */
+    NDT_ICP_REL_MSE = 4,             /* |mse - previous mse| / previous mse < fit_eps (fit_eps > 0)                  */
+    NDT_ICP_NO_CORRESPONDENCES = 5   /* fewer than 3 pairs: converged = 0, the final transformation stays as it was  */
+} ndt_icp_state;
+
+typedef struct {
+    double max_corr_dist;            /* setMaxCorrespondenceDistance   default sqrt(DBL_MAX)   pgo_node: 150        */
+    int max_iter;                    /* setMaximumIterations           default 10              pgo_node: 100        */
+    double trans_eps;                /* setTransformationEpsilon       default 0 (test off)    pgo_node: 1e-6       */
+    double fit_eps;                  /* setEuclideanFitnessEpsilon     default 0 (test off)    pgo_node: 1e-6       */
+} ndt_icp_params;
+
+typedef struct {
+    float final_tf[16];              /* getFinalTransformation(), column-major                                       */
+    int converged;                   /* hasConverged()                                                               */
+    int state;                       /* ndt_icp_state of the last iteration                                          */
+    int nr_iterations;               /* iterations run (transform estimates applied)                                 */
+    double mse;                      /* mean squared pair distance of the last iteration                             */
+    long long n_pairs;               /* pairs of the last iteration                                                  */
+} ndt_icp_result;
+
+/* One iteration: its incremental transform (identity for a NO_CORRESPONDENCES record), pairs, mse and state. */
+typedef struct {
+    float T[16];
+    long long n_pairs;
+    double mse;
+    int state;
+} ndt_icp_record;
+
+ndt_status ndt_icp_default_params(ndt_icp_params* out);
+/* icp.align(output, guess) (pgo_node.cpp:462).  prm NULL = the defaults, guess NULL = identity.  Synchronous. */
+ndt_status ndt_icp_align(ndt_ctx* ctx, const ndt_icp_params* prm, const float guess[16], ndt_icp_result* out);
+/* Per-iteration trace of the last ICP align. */
+ndt_status ndt_icp_history(ndt_ctx* ctx, ndt_icp_record* out, int cap, int* n_out);
+/* Test hook: the correspondences of the last iteration run — per source point the matched target index in the caller's
+ * order (-1: the pair was rejected by max_corr_dist, or the target is empty) and the squared distance to its nearest
+ * target point; *n_out = the source size.  index / d2 may be NULL. */
+ndt_status ndt_icp_correspondences(ndt_ctx* ctx, int* index, float* d2, size_t cap, size_t* n_out);
+/* After ndt_icp_align, ndt_get_output returns the source transformed by the ICP's final transformation, and
+ * ndt_fitness_score with T = NULL scores that transformation (the last align of either kind). */
+
 /* Voxel grid inspection: header = min_b[3], max_b[3], div_b[3], divb_mul[3], n_leaves, n_cloud, overflow,
  * n_valid (16 ints).  Leaves with >= min points (the reference's KD cloud) in ascending key order. */
 ndt_status ndt_grid_info(ndt_ctx* ctx, int header[16]);

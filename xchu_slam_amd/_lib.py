@@ -84,6 +84,39 @@ class FilterParams(C.Structure):
     ]
 
 
+class IcpParams(C.Structure):
+    _fields_ = [
+        ("max_corr_dist", C.c_double),
+        ("max_iter", C.c_int),
+        ("trans_eps", C.c_double),
+        ("fit_eps", C.c_double),
+    ]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [
+        ("final_tf", C.c_float * 16),
+        ("converged", C.c_int),
+        ("state", C.c_int),
+        ("nr_iterations", C.c_int),
+        ("mse", C.c_double),
+        ("n_pairs", C.c_longlong),
+    ]
+
+
+class IcpRecord(C.Structure):
+    _fields_ = [
+        ("T", C.c_float * 16),
+        ("n_pairs", C.c_longlong),
+        ("mse", C.c_double),
+        ("state", C.c_int),
+    ]
+
+
+# ndt_icp_state
+ICP_NOT_CONVERGED, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
+
+
 class OdomParams(C.Structure):
     _fields_ = [
         ("ndt_resolution", C.c_float),
@@ -162,6 +195,10 @@ SIGNATURES = {
     "ndt_fitness_score_async": (C.c_int, [_P, _FP, C.c_double]),
     "ndt_fitness_score_result": (C.c_int, [_P, _DP]),
     "ndt_fitness_index_async": (C.c_int, [_P]),
+    "ndt_icp_default_params": (C.c_int, [C.POINTER(IcpParams)]),
+    "ndt_icp_align": (C.c_int, [_P, C.POINTER(IcpParams), _FP, C.POINTER(IcpResult)]),
+    "ndt_icp_history": (C.c_int, [_P, C.POINTER(IcpRecord), C.c_int, C.POINTER(C.c_int)]),
+    "ndt_icp_correspondences": (C.c_int, [_P, C.POINTER(C.c_int), _FP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ndt_fitness_score_async_cloud": (C.c_int, [_P, _FP, C.c_double, _P, C.c_size_t]),
     "ndt_fitness_score_async_aligned": (C.c_int, [_P, C.c_double, _P, C.c_size_t]),
     "ndt_keyframe_insert_async": (C.c_int, [_P, _FP, _P, C.c_size_t, C.c_float, _P, C.c_size_t, _P, C.c_size_t]),

@@ -24,6 +24,7 @@
 #include "../../include/ndt_hip.h"
 #include "ndt_types.h"
 #include "ndt_linalg.h"
+#include "ndt_icp.h"
 
 namespace ndt {
 // kernels (defined in the other translation units)
@@ -53,7 +54,9 @@ __global__ void k_sor_keep(const float*, int, const double*, int*);
 __global__ void k_ror_keep(const float4*, int, double, int, const GridHeader*, const int*, const int*, const float4*, int*);
 __global__ void k_downsample_finalize(const float4*, const int*, const GridHeader*, float4*);
 __global__ void k_fit_gather(const float4*, const int*, const int*, const int*, const int*, const int*, int, const GridHeader*, float4*,
-                             int*, int*);
+                             int*, int*, int*);
+__global__ void k_icp_pass(float4*, int, IcpState*, const GridHeader*, const int*, const int*, const float4*, const int*, int*, float*,
+                           double*, unsigned*, IcpRecordDev*);
 __global__ void k_fit_block_flags(const int*, const GridHeader*, int*);
 __global__ void k_append2(const float4*, const float4*, int, const GridHeader*, float4*, float4*);
 __global__ void k_fit_block_clear(int*, const GridHeader*);
@@ -216,6 +219,7 @@ struct NNIndex {
     DevBuf<float4> pts;                 // points in (block, cell) order
     DevBuf<int> keys, start;            // per occupied cell: key, first point
     DevBuf<int> blk, off;               // block table + per-occupied-block cell offsets
+    DevBuf<int> idx;                    // per sorted point: its index in the caller's order (built on request: ICP)
 };
 
 struct ndt_ctx {
@@ -364,6 +368,24 @@ struct ndt_ctx {
     PassRecordDev* h_hist = nullptr;
     int h_prof_cap = 0;
     bool have_result = false;
+    // point-to-point ICP (ndt_icp_align): the cumulative cloud X, per-point match / d2 of the last pass, the pass
+    // partials and ticket, the device state and history, pinned state copies ([0] read back, [1] the initial state);
+    // last_icp: the result have_result speaks of is the ICP's (icp_final), not the NDT align's (h_state->T)
+    DevBuf<float4> icp_x;
+    DevBuf<int> icp_match;
+    DevBuf<float> icp_d2;
+    DevBuf<double> icp_part;
+    DevBuf<unsigned> icp_ticket;
+    IcpState* d_icp = nullptr;
+    IcpState* h_icp = nullptr;
+    IcpRecordDev* d_icp_hist = nullptr;
+    bool icp_used = false;              // the fit index of this ctx carries the points' original indices from now on
+    bool last_icp = false;
+    float icp_final[16] = {0};
+    int icp_n = 0;                      // source points of the last ICP align
+    std::vector<IcpRecordDev> icp_hist;
+    hipGraphExec_t icp_graph = nullptr;
+    long long icp_graph_key[12] = {0};
     // graph cache: a few captured chains (different slot counts / buffers), round-robin replacement
     static constexpr int kGraphKey = 23;
     static constexpr int kGraphCache = 64;
@@ -398,6 +420,9 @@ ndt_status fail(ndt_ctx* c, ndt_status st, const std::string& msg) {
 }
 
 Lane main_lane(ndt_ctx* c) { return Lane{c->stream, c->s}; }
+
+// final_transformation_ of the last align, NDT or ICP (valid while have_result)
+const float* last_final(const ndt_ctx* c) { return c->last_icp ? c->icp_final : c->h_state->T; }
 
 #define HIPCHK(ctx, expr)                                                                       \
     do {                                                                                        \
@@ -1360,6 +1385,7 @@ ndt_status align_finish_once(ndt_ctx* c) {
     c->built_since_align = false;
     c->grid_cells_seen = std::max(c->grid_cells_seen, c->h_state->grid_cells);
     c->have_result = true;
+    c->last_icp = false;
     c->align_tgt_gen = c->tgt_gen;
     c->last_passes = c->h_state->n_passes;
     if (!c->h_state->done) return fail(c, NDT_EDEVICE, "align did not finish within the slot budget");
@@ -1745,6 +1771,14 @@ ndt_status ndt_get_output(ndt_ctx* c, float* xyz, size_t stride_bytes) {
     TRY(set_dev(c));
     TRY(flush_source(c));
     TRY(ensure(c, c->out_cloud, c->N));
+    if (c->last_icp) {
+        // an ICP align: the source transformed by its final transformation (PCL returns the cloud it transformed
+        // cumulatively, iteration by iteration: the same points up to f32 rounding)
+        Mat4f Tm;
+        for (int k = 0; k < 16; ++k) Tm.m[k] = c->icp_final[k];
+        hipLaunchKernelGGL(k_transform_mat, dim3(std::max(1, ceil_div(c->N, kBlock))), dim3(kBlock), 0, c->stream, c->source.p, c->N, Tm,
+                           c->out_cloud.p);
+    } else
     hipLaunchKernelGGL(k_transform, dim3(std::max(1, ceil_div(c->N, kBlock))), dim3(kBlock), 0, c->stream, c->source.p, c->N, c->d_state,
                        c->out_cloud.p);
     std::vector<float4> tmp(c->N);
@@ -1858,12 +1892,13 @@ ndt_status ndt_calculate_score(ndt_ctx* c, const float T[16], double* out) {
 // nearest-neighbour index over all target points (built on the first fitness query after a target change)
 // Builds an NNIndex over n device points (cell = base cell size, doubled by k_header until the block-major key range
 // fits).  Uses the ctx's sort scratch; stream-ordered.
-ndt_status enqueue_nn_index(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, float cell, NNIndex& ix) {
+ndt_status enqueue_nn_index(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, float cell, NNIndex& ix, bool want_idx = false) {
     TRY(enqueue_bin_and_sort(c, L, pts, n, dense, ix.hdr, cell, 1));
     TRY(ensure(c, ix.pts, std::max(n, 1))); TRY(ensure(c, ix.keys, std::max(n, 1))); TRY(ensure(c, ix.start, (size_t)n + 1));
+    if (want_idx) TRY(ensure(c, ix.idx, std::max(n, 1)));
     const int nb = std::max(1, std::min(ceil_div(n, kBlock), 4096));
     hipLaunchKernelGGL(k_fit_gather, dim3(nb), dim3(kBlock), 0, L.st, pts, L.s.k0.p, L.s.k1.p, L.s.v0.p, L.s.v1.p,
-                       L.s.seg_start.p, n, ix.hdr, ix.pts.p, ix.keys.p, ix.start.p);
+                       L.s.seg_start.p, n, ix.hdr, ix.pts.p, ix.keys.p, ix.start.p, want_idx ? ix.idx.p : nullptr);
     // occupied blocks: flags -> exclusive scan -> block table + 513 cell offsets per occupied block
     const size_t max_occ = (size_t)std::max(1, std::min(n, kFitMaxBlocks));
     TRY(ensure(c, L.s.flags, std::max(n, 1))); TRY(ensure(c, L.s.cloud_idx, std::max(n, 1)));
@@ -1900,10 +1935,11 @@ ndt_status ensure_fit_index(ndt_ctx* c) {
         c->tgt_ev_valid = true;
     }
     c->fit_ix_gen = c->tgt_gen;
-    c->fit_worker->post([c, pts, M, dense, res]() -> ndt_status {
+    const bool want_idx = c->icp_used;
+    c->fit_worker->post([c, pts, M, dense, res, want_idx]() -> ndt_status {
         HIPCHK(c, hipStreamWaitEvent(c->fit_stream, c->ev_tgt, 0));
         // target points binned in 8x8x8-cell blocks (block-major keys, same stable radix sort as the voxel build)
-        TRY(enqueue_nn_index(c, Lane{c->fit_stream, c->s_fit}, pts, M, dense, res, c->fit_ix));
+        TRY(enqueue_nn_index(c, Lane{c->fit_stream, c->s_fit}, pts, M, dense, res, c->fit_ix, want_idx));
         HIPCHK(c, hipEventRecord(c->ev_fit_tgt, c->fit_stream));
         return NDT_OK;
     });
@@ -1913,7 +1949,7 @@ ndt_status ensure_fit_index(ndt_ctx* c) {
 }
 
 void release_nn_index(NNIndex& ix) {
-    release(ix.pts); release(ix.keys); release(ix.start); release(ix.blk); release(ix.off);
+    release(ix.pts); release(ix.keys); release(ix.start); release(ix.blk); release(ix.off); release(ix.idx);
     if (ix.hdr) (void)hipFree(ix.hdr);
     ix.hdr = nullptr;
 }
@@ -1925,7 +1961,7 @@ static ndt_status fitness_enqueue(ndt_ctx* c, const float* T, double max_range, 
     if (!index_ready) TRY(ensure_fit_index(c));
     // getFitnessScore uses final_transformation_: the last align's result (identity before any align)
     Mat4f Tm;
-    for (int k = 0; k < 16; ++k) Tm.m[k] = T ? T[k] : (c->have_result ? c->h_state->T[k] : (k % 5 == 0 ? 1.f : 0.f));
+    for (int k = 0; k < 16; ++k) Tm.m[k] = T ? T[k] : (c->have_result ? last_final(c)[k] : (k % 5 == 0 ? 1.f : 0.f));
     // the query runs on the fit lane behind the main stream's work so far (the source copy, the align whose transform
     // it applies: the marker is recorded here, on the caller's thread) and beside whatever the main stream queues next
     if (c->lanes_marked & 1) c->lanes_marked &= ~1;  // the caller's mark (ndt_side_lanes_mark)
@@ -1988,13 +2024,13 @@ ndt_status ndt_fitness_score_async_aligned(ndt_ctx* c, double max_range, const f
     TRY(set_dev(c));
     if (c->align_tgt_gen == c->tgt_gen) {  // the target has not changed since the align
         float T[16];
-        for (int k = 0; k < 16; ++k) T[k] = c->h_state->T[k];
+        for (int k = 0; k < 16; ++k) T[k] = last_final(c)[k];
         return fitness_enqueue(c, T, max_range, reinterpret_cast<const float4*>(d_src4), (int)n, false);
     }
     if (c->fit_ix_gen != c->align_tgt_gen || !c->fit_worker || c->fit_worker->failed())
         return fail(c, NDT_EINVAL, "getFitnessScore: the aligned target's index was not queued before setInputTarget");
     float T[16];
-    for (int k = 0; k < 16; ++k) T[k] = c->h_state->T[k];
+    for (int k = 0; k < 16; ++k) T[k] = last_final(c)[k];
     return fitness_enqueue(c, T, max_range, reinterpret_cast<const float4*>(d_src4), (int)n, false, true);
 }
 
@@ -2041,6 +2077,205 @@ ndt_status ndt_fitness_score(ndt_ctx* c, const float T[16], double max_range, do
         }
     }
     return ndt_fitness_score_result(c, out);
+}
+
+// ================================================================ point-to-point ICP (pgo_node's ICPRefine)
+// Defaults of pcl::Registration / pcl::IterativeClosestPoint (PCL 1.7): 10 iterations, sqrt(DBL_MAX) correspondence
+// distance, both epsilons 0 (an epsilon of 0 switches its test off).
+ndt_status ndt_icp_default_params(ndt_icp_params* out) {
+    if (!out) return NDT_EINVAL;
+    out->max_corr_dist = std::sqrt(DBL_MAX);
+    out->max_iter = 10;
+    out->trans_eps = 0.0;
+    out->fit_eps = 0.0;
+    return NDT_OK;
+}
+
+// Passes per graph launch (one state read-back per run).  A run past the converged iteration costs one empty launch per
+// leftover pass (each returns at its first load), a shorter run one host round trip more per run.  Measured on the
+// MI355X with the loop-sized pair of DESIGN.md §4 (15 k points against 163 k, pgo_node's settings, 21 iterations):
+// whole align 1.48 / 1.29 / 1.19 / 1.14 / 1.14 ms at runs of 1 / 2 / 4 / 8 / 16 passes (host wall time, medians of
+// three interleaved repeats, profiles/icp_loop_pair.md): 8 is the shortest run at the floor.
+// NDT_ICP_RUN overrides it for such A/B runs.
+constexpr int kIcpRun = 8;
+
+static ndt_status icp_graph(ndt_ctx* c, int run, int nb, hipGraphExec_t* out) {
+    const long long key[12] = {run, nb, c->N, (long long)(uintptr_t)c->icp_x.p, (long long)(uintptr_t)c->fit_ix.blk.p,
+                               (long long)(uintptr_t)c->fit_ix.off.p, (long long)(uintptr_t)c->fit_ix.pts.p,
+                               (long long)(uintptr_t)c->fit_ix.idx.p, (long long)(uintptr_t)c->icp_match.p,
+                               (long long)(uintptr_t)c->icp_d2.p, (long long)(uintptr_t)c->icp_part.p,
+                               (long long)(uintptr_t)c->icp_ticket.p};
+    if (c->icp_graph && std::memcmp(key, c->icp_graph_key, sizeof(key)) == 0) {
+        *out = c->icp_graph;
+        return NDT_OK;
+    }
+    if (c->icp_graph) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipGraphExecDestroy(c->icp_graph);
+        c->icp_graph = nullptr;
+    }
+    hipGraph_t g;
+    std::unique_lock<std::shared_mutex> capture(c->capture_mu);
+    HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    for (int k = 0; k < run; ++k)
+        hipLaunchKernelGGL(k_icp_pass, dim3(nb), dim3(kIcpBlock), 0, c->stream, c->icp_x.p, c->N, c->d_icp, c->fit_ix.hdr, c->fit_ix.blk.p,
+                           c->fit_ix.off.p, c->fit_ix.pts.p, c->fit_ix.idx.p, c->icp_match.p, c->icp_d2.p, c->icp_part.p,
+                           c->icp_ticket.p, c->d_icp_hist);
+    const hipError_t e_copy = hipMemcpyAsync(&c->h_icp[0], c->d_icp, sizeof(IcpState), hipMemcpyDeviceToHost, c->stream);
+    hipError_t e = hipStreamEndCapture(c->stream, &g);
+    capture.unlock();
+    if (e_copy != hipSuccess) e = e_copy;
+    if (e != hipSuccess) return fail(c, NDT_EDEVICE, std::string("ICP graph capture: ") + hipGetErrorString(e));
+    e = hipGraphInstantiate(&c->icp_graph, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e != hipSuccess) {
+        c->icp_graph = nullptr;
+        return fail(c, NDT_EDEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+    }
+    std::memcpy(c->icp_graph_key, key, sizeof(key));
+    *out = c->icp_graph;
+    return NDT_OK;
+}
+
+// pcl::IterativeClosestPoint::align(output, guess) (pgo_node.cpp:462) over the ctx's target and source.
+ndt_status ndt_icp_align(ndt_ctx* c, const ndt_icp_params* prm, const float guess[16], ndt_icp_result* out) {
+    if (!c || !out) return fail(c, NDT_EINVAL, "null argument");
+    ndt_icp_params p;
+    (void)ndt_icp_default_params(&p);
+    if (prm) p = *prm;
+    if (!(p.max_corr_dist >= 0.0) || !(p.trans_eps >= 0.0) || !(p.fit_eps >= 0.0)) return fail(c, NDT_EINVAL, "invalid ICP params");
+    if (!c->has_target) return fail(c, NDT_ENOTARGET, "no input target");
+    if (!c->has_source || c->N == 0) return fail(c, NDT_ENOSOURCE, "no input source");
+    if (c->al_inflight) return fail(c, NDT_EINVAL, "an asynchronous align is in flight (ndt_align_wait first)");
+    TRY(set_dev(c));
+    TRY(flush_source(c));
+    // the target's nearest-neighbour index (getFitnessScore's), with the points' original indices from now on
+    if (!c->icp_used) {
+        c->icp_used = true;
+        c->fit_valid = false;  // rebuilt behind the fit lane's queued queries (FIFO)
+    }
+    TRY(ensure_fit_index(c));
+    {
+        std::string msg;
+        const ndt_status st = c->fit_worker->take_error(&msg);  // the index build has been issued
+        if (st != NDT_OK) {
+            c->fit_valid = false;
+            c->fit_pending = false;
+            return fail(c, st, "ICP: nearest-neighbour index: " + msg);
+        }
+    }
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_fit_tgt, 0));
+    if (!c->d_icp) {
+        if (hipMalloc(&c->d_icp, sizeof(IcpState)) != hipSuccess || hipMalloc(&c->d_icp_hist, sizeof(IcpRecordDev) * kIcpMaxHistory) != hipSuccess ||
+            hipHostMalloc(&c->h_icp, 2 * sizeof(IcpState), hipHostMallocCoherent) != hipSuccess)
+            return fail(c, NDT_ENOMEM, "ICP state allocation failed");
+    }
+    const int N = c->N;
+    const int nb = std::max(1, std::min(ceil_div(N, kIcpTeams), kIcpMaxBlocks));
+    TRY(ensure(c, c->icp_x, N)); TRY(ensure(c, c->icp_match, N)); TRY(ensure(c, c->icp_d2, N));
+    TRY(ensure(c, c->icp_part, (size_t)kIcpSums * kIcpMaxBlocks));
+    if (!c->icp_ticket.p) {
+        TRY(ensure(c, c->icp_ticket, 64));
+        HIPCHK(c, hipMemsetAsync(c->icp_ticket.p, 0, c->icp_ticket.cap * sizeof(unsigned), c->stream));
+    }
+    // X = the source (transformed by the guess in the first pass, unless the guess is the identity)
+    TRY(copy16(c, c->stream, c->icp_x.p, c->source.p, (size_t)N * sizeof(float4)));
+    IcpState* s0 = &c->h_icp[1];
+    std::memset(s0, 0, sizeof(IcpState));
+    s0->max_corr2 = p.max_corr_dist * p.max_corr_dist;
+    s0->trans_eps = p.trans_eps;
+    s0->fit_eps = p.fit_eps;
+    s0->max_iter = p.max_iter;
+    s0->min_pairs = 3;
+    s0->prev_mse = DBL_MAX;
+    bool identity = true;
+    for (int k = 0; k < 16; ++k) {
+        const float v = guess ? guess[k] : (k % 5 == 0 ? 1.f : 0.f);
+        s0->T[k] = v;
+        s0->final_tf[k] = v;
+        identity = identity && v == (k % 5 == 0 ? 1.f : 0.f);
+    }
+    s0->apply = identity ? 0 : 1;
+    HIPCHK(c, hipMemcpyAsync(c->d_icp, s0, sizeof(IcpState), hipMemcpyHostToDevice, c->stream));
+    static const int run_env = [] {
+        const char* e = std::getenv("NDT_ICP_RUN");  // A/B runs
+        return e ? std::max(1, std::min(64, std::atoi(e))) : kIcpRun;
+    }();
+    const int run = run_env;
+    hipGraphExec_t gx = nullptr;
+    TRY(icp_graph(c, run, nb, &gx));
+    const int max_rounds = std::max(p.max_iter, 1) / run + 2;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c->profiling) {
+        HIPCHK(c, hipEventCreate(&e0));
+        HIPCHK(c, hipEventCreate(&e1));
+        HIPCHK(c, hipEventRecord(e0, c->stream));
+    }
+    c->have_result = false;
+    bool finished = false;
+    for (int round = 0; round < max_rounds && !finished; ++round) {
+        HIPCHK(c, hipGraphLaunch(gx, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        finished = c->h_icp[0].done != 0;
+    }
+    if (e0) {
+        HIPCHK(c, hipEventRecord(e1, c->stream));
+        HIPCHK(c, hipEventSynchronize(e1));
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
+        c->ms_align = ms;
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    if (!finished) return fail(c, NDT_EDEVICE, "ICP did not finish within its iteration budget");
+    int ix_err = 0;  // the index sort's error bits, as k_fitness reports them through its count
+    HIPCHK(c, hipMemcpy(&ix_err, &c->fit_ix.hdr->pad[0], sizeof(int), hipMemcpyDeviceToHost));
+    if (ix_err) {
+        c->fit_valid = false;
+        return fail(c, NDT_EDEVICE, "ICP: nearest-neighbour index sort: radix look-back timed out");
+    }
+    const IcpState& s = c->h_icp[0];
+    c->icp_hist.resize(std::min(s.hist_count, kIcpMaxHistory));
+    if (!c->icp_hist.empty())
+        HIPCHK(c, hipMemcpy(c->icp_hist.data(), c->d_icp_hist, c->icp_hist.size() * sizeof(IcpRecordDev), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 16; ++k) {
+        c->icp_final[k] = s.final_tf[k];
+        out->final_tf[k] = s.final_tf[k];
+    }
+    out->converged = s.converged;
+    out->state = s.conv_state;
+    out->nr_iterations = s.iterations;
+    out->mse = s.mse;
+    out->n_pairs = s.pairs;
+    c->icp_n = N;
+    c->last_icp = true;
+    c->have_result = true;
+    c->align_tgt_gen = c->tgt_gen;
+    return NDT_OK;
+}
+
+ndt_status ndt_icp_history(ndt_ctx* c, ndt_icp_record* out, int cap, int* n_out) {
+    if (!c || !n_out || (cap > 0 && !out)) return fail(c, NDT_EINVAL, "bad history args");
+    const int n = std::min((int)c->icp_hist.size(), std::max(cap, 0));
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < 16; ++k) out[i].T[k] = c->icp_hist[i].T[k];
+        out[i].n_pairs = c->icp_hist[i].pairs;
+        out[i].mse = c->icp_hist[i].mse;
+        out[i].state = c->icp_hist[i].conv_state;
+    }
+    *n_out = (int)c->icp_hist.size();
+    return NDT_OK;
+}
+
+ndt_status ndt_icp_correspondences(ndt_ctx* c, int* index, float* d2, size_t cap, size_t* n_out) {
+    if (!c || !n_out) return fail(c, NDT_EINVAL, "null argument");
+    if (!c->icp_n || !c->icp_match.p) return fail(c, NDT_EINVAL, "no ICP align");
+    TRY(set_dev(c));
+    const size_t n = std::min((size_t)c->icp_n, cap);
+    if (index && n) HIPCHK(c, hipMemcpy(index, c->icp_match.p, n * sizeof(int), hipMemcpyDeviceToHost));
+    if (d2 && n) HIPCHK(c, hipMemcpy(d2, c->icp_d2.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    *n_out = (size_t)c->icp_n;
+    return NDT_OK;
 }
 
 ndt_status ndt_keyframe_insert_async(ndt_ctx* c, const float T[16], const float* d_scan4, size_t n, float leaf, float* d_map_a, size_t n_a,
@@ -2652,6 +2887,11 @@ void ndt_destroy(ndt_ctx* c) {
     if (c->h_rb) (void)hipHostFree(c->h_rb);
     if (c->d_clk) (void)hipFree(c->d_clk);
     if (c->d_hist) (void)hipFree(c->d_hist);
+    if (c->icp_graph) (void)hipGraphExecDestroy(c->icp_graph);
+    release(c->icp_x); release(c->icp_match); release(c->icp_d2); release(c->icp_part); release(c->icp_ticket);
+    if (c->d_icp) (void)hipFree(c->d_icp);
+    if (c->h_icp) (void)hipHostFree(c->h_icp);
+    if (c->d_icp_hist) (void)hipFree(c->d_icp_hist);
     for (auto e : {c->ev_tgt, c->ev_main_fit, c->ev_main_ins, c->ev_fit_src, c->ev_fit_tgt}) if (e) (void)hipEventDestroy(e);
     for (auto e : c->pass_ev) (void)hipEventDestroy(e);
     for (hipStream_t st : {c->stream, c->fit_stream, c->ins_stream}) if (st) (void)hipStreamDestroy(st);

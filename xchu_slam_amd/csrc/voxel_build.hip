@@ -1208,13 +1208,19 @@ __global__ __launch_bounds__(kBlock) void k_fit_gather(const float4* __restrict_
                                                        const int* __restrict__ k1, const int* __restrict__ v0,
                                                        const int* __restrict__ v1, const int* __restrict__ seg_start, int n,
                                                        const GridHeader* __restrict__ h, float4* __restrict__ fit_pts,
-                                                       int* __restrict__ fit_keys, int* __restrict__ fit_start) {
+                                                       int* __restrict__ fit_keys, int* __restrict__ fit_start,
+                                                       int* __restrict__ fit_idx) {
     if (h->empty) return;
     const int* keys = sorted_buf(h, k0, k1);
     const int* vals = sorted_buf(h, v0, v1);
     const int nl = h->n_leaves;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-        if (i < h->n_points) fit_pts[i] = pts[vals[i]];
+        if (i < h->n_points) {
+            fit_pts[i] = pts[vals[i]];
+            // the point's index in the caller's order, for a reader that reports which point matched (k_icp_pass); NULL
+            // for the others
+            if (fit_idx) fit_idx[i] = vals[i];
+        }
         if (i < nl) {
             fit_start[i] = seg_start[i];
             fit_keys[i] = keys[seg_start[i]];
