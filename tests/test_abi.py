@@ -33,8 +33,9 @@ def test_library_exports_every_declared_symbol():
     missing = [s for s in declared_symbols() if not hasattr(lib, s)]
     assert not missing, missing
     out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\sT\s(ndt_\w+)", out))
-    assert set(declared_symbols()) <= exported
+    # the unmangled function symbols are the C-ABI and nothing else: an internal helper with C linkage would show here
+    exported = {name for kind, name in re.findall(r"^\S+\s+(\S)\s+(\S+)$", out, re.M) if kind == "T" and not name.startswith("_Z")}
+    assert exported == set(declared_symbols()), sorted(exported ^ set(declared_symbols()))
 
 
 def test_abi_version_matches_header():

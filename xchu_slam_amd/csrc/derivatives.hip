@@ -12,6 +12,7 @@
 // reduced by a fixed wave butterfly + LDS into per-workgroup partials.  No atomics => bitwise
 // run-to-run determinism.  Memory-bound gather + reduction, no MFMA.
 #include "ndt_control.h"
+#include "ndt_kernels.h"
 
 namespace ndt {
 

@@ -16,6 +16,7 @@
 // insertion), merged in ascending order at the end;
 // the threshold statistics are one fixed-order f64 reduction (deterministic).  Integer / gather work, no MFMA.
 #include "ndt_device.h"
+#include "ndt_kernels.h"
 
 namespace ndt {
 

@@ -18,6 +18,7 @@
 #include "ndt_types.h"
 #include "ndt_linalg.h"
 #include "ndt_icp.h"
+#include "ndt_kernels.h"
 
 namespace ndt {
 

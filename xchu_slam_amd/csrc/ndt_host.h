@@ -1,0 +1,400 @@
+// ndt_host.h — what the host units of the library share (internal; the C-ABI is include/ndt_hip.h): the context, its
+// buffers and lanes, the error helpers, and the host functions that cross unit boundaries.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <string>
+#include <vector>
+#include <cstring>
+#include <cstdlib>
+#include <cstdio>
+#include <algorithm>
+#include <cmath>
+#include <atomic>
+#include <condition_variable>
+#include <deque>
+#include <functional>
+#include <mutex>
+#include <shared_mutex>
+#include <thread>
+
+#include "../../include/ndt_hip.h"
+#include "ndt_kernels.h"
+
+namespace ndt::host {
+
+constexpr int kTileKeys = kBlock * 16;
+
+// A device buffer that owns its memory: freed with its owner (the ctx, a lane's scratch, a call's temporaries)
+template <typename T> struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+struct Scratch {
+    DevBuf<int> k0, v0, k1, v1, radix_aux, seg_start, flags, cloud_idx;
+    DevBuf<int2> cloud_span;
+    DevBuf<unsigned> radix_status;
+    DevBuf<float> mm;
+    DevBuf<float4> sorted_pts;   // points gathered into voxel order (VoxelGrid filter)
+    DevBuf<unsigned long long> scan_status;   // single-pass scan look-back words (epoch-tagged, never cleared)
+    DevBuf<unsigned long long> scan_ticket;   // monotone tile ticket of the single-pass scan
+    unsigned long long scan_tickets = 0;      // host copy of the ticket counter
+    unsigned scan_epoch = 0;
+};
+
+// Where a sort / scan runs: a stream and the scratch its kernels own (radix buffers, look-back words).  The ctx's
+// main stream owns ndt_ctx::s; getFitnessScore (index build + query) and the keyframe insertion run on side lanes with
+// scratch of their own, so that odom_node's per-scan tail overlaps the main stream's target build and align (C3).
+struct Lane {
+    hipStream_t st;
+    Scratch& s;
+};
+
+// The host thread of a side lane: the lane's launches (a sort is ~13 kernels, ~4 us of host time each) are issued from
+// it in FIFO order, so the caller only records a main-stream marker and posts the job.  A job's failure is kept until
+// the lane's result call (take_error).
+struct LaneWorker {
+    std::thread th;
+    std::mutex mu;
+    std::condition_variable cv_job, cv_idle;
+    std::deque<std::function<ndt_status()>> jobs;
+    int pending = 0;
+    bool stop = false;
+    ndt_status st = NDT_OK;  // first failure not yet taken
+    std::string msg;
+    int device = 0;
+    std::shared_mutex* capture_mu;  // the ctx's align-graph capture lock, held shared while a job runs (see ndt_ctx::capture_mu)
+
+    LaneWorker(int dev, std::shared_mutex* cap) : device(dev), capture_mu(cap) { th = std::thread([this] { run(); }); }
+    ~LaneWorker() {
+        {
+            std::lock_guard<std::mutex> g(mu);
+            stop = true;
+        }
+        cv_job.notify_one();
+        th.join();
+    }
+    void post(std::function<ndt_status()> f) {
+        {
+            std::lock_guard<std::mutex> g(mu);
+            jobs.push_back(std::move(f));
+            ++pending;
+        }
+        cv_job.notify_one();
+    }
+    // waits until every posted job has been issued; returns the pending failure (kept)
+    ndt_status drain(std::string* err) {
+        std::unique_lock<std::mutex> g(mu);
+        cv_idle.wait(g, [this] { return pending == 0; });
+        if (st != NDT_OK && err) *err = msg;
+        return st;
+    }
+    // a job failed and its failure has not been taken yet (non-blocking)
+    bool failed() {
+        std::lock_guard<std::mutex> g(mu);
+        return st != NDT_OK;
+    }
+    ndt_status take_error(std::string* err) {
+        const ndt_status s = drain(err);
+        std::lock_guard<std::mutex> g(mu);
+        st = NDT_OK;
+        return s;
+    }
+    void run();  // host_lanes.hip
+};
+
+inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// Exact nearest-neighbour index over a cloud (block-major binning, layout 1 of k_header): the points sorted into
+// 8x8x8-cell blocks, a block table and per-occupied-block cell offsets.
+struct NNIndex {
+    GridHeader* hdr = nullptr;          // binning (device)
+    DevBuf<float4> pts;                 // points in (block, cell) order
+    DevBuf<int> keys, start;            // per occupied cell: key, first point
+    DevBuf<int> blk, off;               // block table + per-occupied-block cell offsets
+    DevBuf<int> idx;                    // per sorted point: its index in the caller's order (built on request: ICP)
+};
+
+}  // namespace ndt::host
+
+using namespace ndt;
+using namespace ndt::host;
+
+struct ndt_ctx {
+    ndt_params prm{};
+    int device = 0;
+    int n_cu = 256;  // compute units the main stream's passes spread over (direct-pass grid)
+    // CU partition (NDT_LANE_CUS, A/B): the side lanes run on lane_mask's CUs, the main stream on the others
+    std::vector<uint32_t> lane_mask;
+    hipStream_t stream = nullptr;
+    std::string err;
+    // target grid
+    DevBuf<float4> target;            // owned copy for host-provided targets
+    const float4* target_ptr = nullptr;  // points the build reads (owned copy or the caller's device buffer)
+    int M = 0;
+    int target_dense = 1;
+    bool has_target = false;
+    bool grid_valid = false;
+    float grid_res = 0.f;
+    GridHeader* d_hdr = nullptr;
+    GridHeader* d_hdr_ds = nullptr;
+    GridHeader* d_hdr_fe = nullptr;  // the filter's compaction scans: pad[0] look-back timeout flag, pad[1] kept count
+    NNIndex fit_ix;                     // nearest-neighbour index over the target (getFitnessScore)
+    NNIndex sor_ix;                     // nearest-neighbour index over a filtered scan (StatisticalOutlierRemoval)
+    DevBuf<int> fit_cnt;
+    DevBuf<unsigned> fit_ticket;        // last-workgroup ticket of k_fitness (re-armed by that workgroup)
+    // asynchronous getFitnessScore / keyframe insertion: results land in pinned memory, an event marks them
+    struct AsyncOut {
+        double fit_sum;
+        long long fit_cnt;
+        GridHeader ins_hdr;
+        int fe_words[4];  // ndt_filter_scan_device: [0] scan flag, [1] scan count, [2] outlier index sort flag
+    };
+    AsyncOut* d_async = nullptr;
+    AsyncOut* h_async = nullptr;        // pinned
+    hipEvent_t ev_fit = nullptr, ev_ins = nullptr;
+    bool fit_pending = false, ins_pending = false;
+    // side lanes (created on first use): fit_stream runs getFitnessScore's index build and query, ins_stream the
+    // keyframe insertion, each issued by its own host thread.  ev_tgt marks (main stream) the current target's points in
+    // place — recorded ahead of each build, the index build waits on it, not on the voxel build; ev_main_* are the
+    // main-stream markers a side-lane job waits on; ev_fit_src / ev_fit_tgt mark (fit_stream) the end of the last query
+    // that read the ctx's source / of the last index build that read the ctx's target points (main waits on them
+    // before it rewrites what the index or query read)
+    hipStream_t fit_stream = nullptr, ins_stream = nullptr;
+    LaneWorker* fit_worker = nullptr;   // host threads issuing the side lanes' launches
+    LaneWorker* ins_worker = nullptr;
+    Scratch s_fit, s_ins;
+    GridHeader* d_hdr_ins = nullptr;    // keyframe insertion's VoxelGrid binning
+    hipEvent_t ev_tgt = nullptr, ev_main_fit = nullptr, ev_main_ins = nullptr, ev_fit_src = nullptr, ev_fit_tgt = nullptr;
+    int lanes_marked = 0;  // ndt_side_lanes_mark: bit 0 the next fitness query, bit 1 the next insertion use ev_main_fit as is
+    bool fit_src_used = false, fit_tgt_used = false;
+    // held exclusively while the main stream captures an align graph and shared while a lane thread runs a job: a stream
+    // wait issued by a lane thread during the capture is rejected by the runtime ("dependency created on uncaptured
+    // work"), and the lanes' allocations (hipMalloc / hipFree on growth) stay out of it too; the two lanes issue side by
+    // side
+    std::shared_mutex capture_mu;
+    int fit_n = 0;                      // source points of the last query
+    size_t ins_n_in = 0;
+    DevBuf<float4> ins_tr, ins_ds;      // keyframe insertion scratch (transformed scan, VoxelGrid output)
+    DevBuf<double> fit_sum;
+    DevBuf<float> fit_d2;
+    bool fit_valid = false;             // index matches the current target
+    GridHeader* h_hdr = nullptr;  // pinned
+    bool tgt_ev_valid = false;  // ev_tgt marks the current target (recorded by build_target once the fit lane is in use)
+    Scratch s;
+    // merge-extended targets (ndt_set_target_append_device): the new points' sort scratch, the previous header, and whether
+    // s's sorted keys / indices and d_hdr still describe the current target (no other main-stream sort since its build)
+    Scratch s_inc;
+    GridHeader* d_hdr_prev = nullptr;
+    bool inc_ok = false;
+    // target-build robustness (GridHeader::pad[0] bits, checked by the align read-back or settle_build): radix passes
+    // launched = the key width of the last grid read back, +1 bit of margin (radix_pred; 4 until a grid was seen);
+    // radix_force (ndt_set_build_options test hook) fixes the count; tile_tickets (sticky once a look-back timed out, or
+    // set by the hook) takes every sort's tiles by atomic ticket; counters for ndt_build_stats
+    int radix_pred = 4, radix_force = 0;
+    bool tile_tickets = false;
+    bool build_unchecked = false;   // a target build queued whose error bits no align / settle_build has read yet
+    bool rerun_full = false;        // a re-run build: all four radix passes whatever the prediction or the hook says
+    float al_guess[16] = {0};       // the guess of the align in flight (re-run after a flagged build)
+    int al_berr = 0;                // build error bits the align's read-back found (align_finish_once)
+    long long n_builds_full = 0, n_builds_merge = 0, n_builds_rerun = 0, n_rerun_lookback = 0;
+    // target generations (one per setInputTarget): of the current target, of the one the fit index was last queued
+    // for, and of the one the last align result belongs to (ndt_fitness_score_async_aligned)
+    unsigned long long tgt_gen = 0, fit_ix_gen = ~0ull, align_tgt_gen = ~0ull;
+    DevBuf<VoxelRec> recs;
+    DevBuf<float4> cent;
+    DevBuf<double> icovd, evals;
+    DevBuf<int> cloud_key;
+    DevBuf<int> valid_part;             // usable-voxel count per finalize wave (summed by ndt_grid_info)
+    DevBuf<int2> table;
+    unsigned max_log2cap = 6;
+    DevBuf<int> grid;                   // dense cell -> cloud index grid (used when the bbox fits)
+    long long grid_cells_seen = 0;      // largest target cell count read back (align, single pass, grid info): sizes the grid
+    // source
+    DevBuf<float4> source;
+    int N = 0;
+    bool has_source = false;
+    const float4* src_pend = nullptr;   // ndt_set_source_device's copy, deferred to the next align (its k_align_init) or flush_source
+    // source in target-cell order for the passes of an align (k_src_keys): the cloud the pass kernels read
+    DevBuf<float4> source_ord;
+    DevBuf<int> ord_k0, ord_v0, ord_k1, ord_v1;
+    const float4* pass_src = nullptr;
+    bool order_source = true;
+    // pass-chain options (ndt_set_pass_options): leading-tail chains where an align is latency-bound, two points per
+    // thread in large last-workgroup-tail passes
+    bool opt_lead_tail = true;
+    int opt_ppt = 2;
+    // filter_node front end (ndt_filter_scan): scratch + the last call's SOR statistics
+    DevBuf<int> fe_flags, fe_idx;
+    DevBuf<float4> fe_in, fe_crop, fe_ds, fe_out;
+    DevBuf<float> fe_dist;
+    DevBuf<double> fe_thr;
+    size_t fe_nvox = 0;
+    // align
+    AlignState* d_state = nullptr;
+    // leading-tail chains (k_pass_lead): the second state / partials buffer of the ping-pong and the parity of the next
+    // kernel of the align in flight (kernel j reads state j & 1, writes state (j + 1) & 1, writes partials j & 1)
+    AlignState* d_state2 = nullptr;
+    int lead = 0, lead_par = 0;
+    bool no_lead = false;  // batched replay: several aligns in flight share the CUs, the redundant tails would cost CU time
+    AlignState* h_state = nullptr;  // pinned (coherent), written by k_readback
+    // read-back words (pinned, coherent): [0] sequence number of the last finished round, [1..2] device clock of the
+    // align's start / that round's end (100 MHz); d_clk[0]: the start stamp k_align_init takes
+    unsigned long long* h_rb = nullptr;
+    unsigned long long* d_clk = nullptr;
+    unsigned long long rb_seq = 0, al_seq = 0;
+    DevBuf<double> partials;
+    DevBuf<double> partials2;  // leading-tail chains: the other partials buffer
+    DevBuf<int4> nbr;                   // DIRECT7 neighbour cache of the align's source points (2 x int4 per point)
+    DevBuf<double> score_part;          // calculateScore per-workgroup partial sums
+    // gauss_d1_/d2_/d3_ as the reference holds them: set by the constructor for resolution 1.0 / outlier 0.55
+    // (ndt_omp_impl.hpp:46-63) and recomputed at the start of every align (:80-87); calculateScore reads them
+    double gauss_cur[3] = {0.0, 0.0, 0.0};
+    DevBuf<double> reduce_out;
+    DevBuf<unsigned> counter;           // last-workgroup ticket of the pass epilogue (re-armed by the last workgroup)
+    PassRecordDev* d_hist = nullptr;
+    int hist_cap = kMaxHistory;
+    DevBuf<float4> out_cloud;
+    DevBuf<unsigned long long> ts;      // per-pass kTsStride s_memrealtime stamps (profiling)
+    double prof_phase_sum[7] = {0, 0, 0, 0, 0, 0, 0};
+    int prof_phase_count = 0;
+    double prof_body_sum[5] = {0, 0, 0, 0, 0};
+    int prof_body_count = 0;
+    double prof_tail_sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int prof_tail_count = 0;
+    unsigned long long* h_ts = nullptr;  // pinned copies, filled by k_readback before the align's sync
+    PassRecordDev* h_hist = nullptr;
+    int h_prof_cap = 0;
+    bool have_result = false;
+    // point-to-point ICP (ndt_icp_align): the cumulative cloud X, per-point match / d2 of the last pass, the pass
+    // partials and ticket, the device state and history, pinned state copies ([0] read back, [1] the initial state);
+    // last_icp: the result have_result speaks of is the ICP's (icp_final), not the NDT align's (h_state->T)
+    DevBuf<float4> icp_x;
+    DevBuf<int> icp_match;
+    DevBuf<float> icp_d2;
+    DevBuf<double> icp_part;
+    DevBuf<unsigned> icp_ticket;
+    IcpState* d_icp = nullptr;
+    IcpState* h_icp = nullptr;
+    IcpRecordDev* d_icp_hist = nullptr;
+    bool icp_used = false;              // the fit index of this ctx carries the points' original indices from now on
+    bool last_icp = false;
+    float icp_final[16] = {0};
+    int icp_n = 0;                      // source points of the last ICP align
+    std::vector<IcpRecordDev> icp_hist;
+    hipGraphExec_t icp_graph = nullptr;
+    long long icp_graph_key[12] = {0};
+    // graph cache: a few captured chains (different slot counts / buffers), round-robin replacement
+    static constexpr int kGraphKey = 23;
+    static constexpr int kGraphCache = 64;
+    struct GraphEntry {
+        hipGraphExec_t exec = nullptr;
+        long long key[kGraphKey] = {0};
+    };
+    GraphEntry graphs[kGraphCache];  // scans of a few neighbouring size buckets (geom_points) x both lead parities
+    int graph_next = 0;
+    int last_passes = 0;                // passes of the previous align: sizes the first graph round of the next
+    // timing
+    bool built_since_align = false;  // ms_build: a target build was queued since the last align
+    std::vector<hipEvent_t> pass_ev;
+    bool profiling = false;
+    double ms_build = 0, ms_align = 0, ms_pass_avg = 0, pass_bytes_avg = 0;
+    double prof_ms_sum = 0, prof_bytes_sum = 0;
+    long long prof_count = 0;
+    std::vector<PassRecordDev> last_hist;
+    // align in flight (align_enqueue -> align_finish)
+    bool al_inflight = false, al_mt = false;
+    int al_full = 0, al_slots = 0;
+    // helper contexts of the batched replay (one stream each), created on first use
+    std::vector<ndt_ctx*> helpers;
+};
+
+namespace ndt::host {
+
+// sets the error text of the call (the ctx's, or on a side lane's host thread that thread's own) and returns st
+ndt_status fail(ndt_ctx* c, ndt_status st, const std::string& msg);
+
+inline Lane main_lane(ndt_ctx* c) { return Lane{c->stream, c->s}; }
+
+// final_transformation_ of the last align, NDT or ICP (valid while have_result)
+inline const float* last_final(const ndt_ctx* c) { return c->last_icp ? c->icp_final : c->h_state->T; }
+
+#define HIPCHK(ctx, expr)                                                                       \
+    do {                                                                                        \
+        hipError_t _e = (expr);                                                                 \
+        if (_e != hipSuccess)                                                                   \
+            return fail(ctx, NDT_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));   \
+    } while (0)
+
+template <typename T> ndt_status ensure(ndt_ctx* c, DevBuf<T>& b, size_t n) {
+    if (n == 0) n = 1;
+    if (b.cap >= n) return NDT_OK;
+    const size_t want = std::max(n, b.cap + b.cap / 2);
+    if (b.p) HIPCHK(c, hipFree(b.p));
+    b.p = nullptr;
+    b.cap = 0;
+    if (hipMalloc(&b.p, want * sizeof(T)) != hipSuccess) {
+        b.p = nullptr;
+        return fail(c, NDT_ENOMEM, "hipMalloc failed");
+    }
+    b.cap = want;
+    return NDT_OK;
+}
+
+// frees early (a DevBuf otherwise lives as long as its owner)
+template <typename T> void release(DevBuf<T>& b) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+
+#define TRY(expr)                          \
+    do {                                   \
+        ndt_status _s = (expr);            \
+        if (_s != NDT_OK) return _s;       \
+    } while (0)
+
+inline ndt_status set_dev(ndt_ctx* c) {
+    HIPCHK(c, hipSetDevice(c->device));
+    return NDT_OK;
+}
+
+// what every registration call needs: a target and a non-empty source
+inline ndt_status need_target_and_source(ndt_ctx* c) {
+    if (!c->has_target) return fail(c, NDT_ENOTARGET, "no input target");
+    if (!c->has_source || c->N == 0) return fail(c, NDT_ENOSOURCE, "no input source");
+    return NDT_OK;
+}
+
+// host_sort.hip
+ndt_status scan_ctx(ndt_ctx* c, Lane L, int nb, ScanCtx* sc);
+ndt_status enqueue_scan(ndt_ctx* c, Lane L, const int* in, int n_host, const int* n_dev, int* out, int* total_out, GridHeader* herr);
+int radix_items(const ndt_ctx* c, int n);
+size_t radix_status_words(int nb);
+void launch_radix_pass(const ndt_ctx* c, Lane L, int items, int nb, int* k0, int* v0, int* k1, int* v1, int n, int pass,
+                       const GridHeader* h, GridHeader* herr, int last_pass = 3);
+int radix_launch_passes(const ndt_ctx* c);
+void note_grid_width(ndt_ctx* c, long long cells, int dense);
+ndt_status enqueue_bin_and_sort(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, GridHeader* h, float leaf, int layout = 0,
+                                int binning = 0, int2* cloud_span = nullptr, int passes = 4);
+ndt_status enqueue_downsample_finalize(ndt_ctx* c, Lane L, const GridHeader* h, const float4* in, int n, float4* out);
+// host_target.hip
+ndt_status build_target(ndt_ctx* c);
+ndt_status rerun_build(ndt_ctx* c, int berr);
+ndt_status settle_build(ndt_ctx* c);
+ndt_status upload_points(ndt_ctx* c, DevBuf<float4>& dst, const float* xyz, size_t n, size_t stride_bytes);
+// host_align.hip
+void invalidate_graph(ndt_ctx* c);
+ndt_status copy16(ndt_ctx* c, hipStream_t stream, void* dst, const void* src, size_t bytes);
+ndt_status flush_source(ndt_ctx* c);
+ndt_status capture_graph(ndt_ctx* c, const char* end_what, const std::function<ndt_status()>& body, hipGraphExec_t* out);
+// host_lanes.hip
+ndt_status main_after_fit(ndt_ctx* c, bool source);
+ndt_status enqueue_nn_index(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, float cell, NNIndex& ix, bool want_idx = false);
+ndt_status ensure_fit_index(ndt_ctx* c);
+
+}  // namespace ndt::host

@@ -1,4 +1,4 @@
-// ndt_icp.h — device-resident state of the point-to-point ICP operator (icp.hip, ndt_api.hip).
+// ndt_icp.h — device-resident state of the point-to-point ICP operator (icp.hip, host_icp.hip).
 //
 // pcl::IterativeClosestPoint as pgo_node's PGO::ICPRefine drives it (pgo_node.cpp:404-483): one k_icp_pass launch per
 // iteration, the whole control flow (pair count test, Umeyama estimate, final transform, convergence criteria) in the

@@ -132,7 +132,7 @@ struct GridHeader {
     int flip;
     int pad2;
 };
-// GridHeader::pad[0] bits: the build ran but its sort may be wrong, and is re-run (ndt_api.hip align_finish)
+// GridHeader::pad[0] bits: the build ran but its sort may be wrong, and is re-run (host_align.hip align_finish)
 constexpr int kBuildErrLookback = 1;  // a decoupled look-back timed out (a predecessor tile not resident): re-run with tickets
 constexpr int kBuildErrPasses = 2;    // the key needs more radix passes than were launched: re-run with all four
 constexpr int kBuildErrMerge = 4;     // a merge-extended build beyond the exact cell remap (|cell| >= 2^23): re-run fresh

@@ -5,6 +5,7 @@
 // the derivative-pass kernels (derivatives.hip): in the last workgroup of a pass, or at the start of the next pass's
 // kernel (leading-tail chains).
 #include "ndt_control.h"
+#include "ndt_kernels.h"
 
 namespace ndt {
 

@@ -12,6 +12,7 @@
 // HBM-bound integer/byte work: coalesced tiles of 4096 keys per workgroup, LDS digit counters, wave ballots
 // for stable in-wave ranks; no atomics on data (counts only), so the result is bitwise deterministic.
 #include "ndt_device.h"
+#include "ndt_kernels.h"
 
 namespace ndt {
 
@@ -302,7 +303,7 @@ constexpr unsigned kStCnt = (1u << 30) - 1u;
 // four time-outs of C4's 16-queue x 8-stream run waited ~2 s (profiles/r06/c4_queues)
 constexpr int kSpinLimit = 1 << 15;
 // Sorts of at most kTwoLevelTiles tiles (every sort whose tiles can all be resident) resolve the look-back in two levels
-// over groups of kGroupTiles tiles; the group totals sit behind the tiles' words: [4 passes][groups][256] (ndt_api.hip
+// over groups of kGroupTiles tiles; the group totals sit behind the tiles' words: [4 passes][groups][256] (host_sort.hip
 // radix_status_words)
 #ifndef NDT_TWOLEVEL_TILES
 #define NDT_TWOLEVEL_TILES 1024
@@ -380,7 +381,7 @@ __global__ __launch_bounds__(kBlock) void k_radix_onesweep(int* __restrict__ k0,
                                                            GridHeader* __restrict__ herr, int last_pass, int tickets) {
     static_assert(kBlock == 256, "thread = digit");
     // the host launches as many passes as it predicts the key needs (the previous grid's width): the last
-    // launched pass flags a key that needs more, and the build is re-run with all four (ndt_api.hip align_finish)
+    // launched pass flags a key that needs more, and the build is re-run with all four (host_align.hip align_finish)
     if (pass == last_pass && pass < 3 && blockIdx.x == 0 && threadIdx.x == 0 && radix_pass_active(h, pass + 1))
         atomicOr(&herr->pad[0], kBuildErrPasses);
     if (!radix_pass_active(h, pass)) return;
