@@ -22,9 +22,10 @@ extern "C" {
 
 /* Layout version of the structs below and of the buffers the library writes through caller pointers
  * (ndt_result, ndt_pass_record, ndt_pair_desc, ndt_filter_params, ndt_pass_phases' 22 doubles).  History: 1 = round 1;
- * 2 = ndt_result.solver_fallbacks appended, ndt_pass_phases 20 -> 22 doubles.  A caller built against this header
- * checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
-#define NDT_HIP_ABI_VERSION 2
+ * 2 = ndt_result.solver_fallbacks appended, ndt_pass_phases 20 -> 22 doubles; 3 = the Scan Context surface (ndt_sc_params,
+ * ndt_sc_result; no earlier layout changed).  A caller built against this header checks
+ * ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
+#define NDT_HIP_ABI_VERSION 3
 
 typedef struct ndt_ctx ndt_ctx;
 
@@ -182,7 +183,7 @@ ndt_status ndt_fitness_index_async(ndt_ctx* ctx);
  * index), pairs with d^2 <= max_corr_dist^2 kept, fewer than 3 pairs = NDT_ICP_NO_CORRESPONDENCES; Umeyama estimate
  * without scale (f64 sums and SVD where PCL has f32: documented deviation), applied in f32 to the cloud and to the final
  * transformation; then the criteria in the order of ndt_icp_state, the first that holds ends the align.  These additions
- * leave every existing layout as it is (NDT_HIP_ABI_VERSION stays 2). */
+ * left every existing layout as it was. */
 typedef enum {
     NDT_ICP_NOT_CONVERGED = 0,
     NDT_ICP_ITERATIONS = 1,          /* iterations >= max_iter                                                      */
@@ -227,6 +228,63 @@ ndt_status ndt_icp_history(ndt_ctx* ctx, ndt_icp_record* out, int cap, int* n_ou
 ndt_status ndt_icp_correspondences(ndt_ctx* ctx, int* index, float* d2, size_t cap, size_t* n_out);
 /* After ndt_icp_align, ndt_get_output returns the source transformed by the ICP's final transformation, and
  * ndt_fitness_score with T = NULL scores that transformation (the last align of either kind). */
+
+/* ---- Scan Context: SCManager (xchu_mapping/include/scancontext/Scancontext.{h,cpp}), pgo_node's default loop detector
+ * (loop_method 1: makeAndSaveScancontextAndKeys per keyframe at pgo_node.cpp:236, detectLoopClosureID at :344).  The
+ * descriptors (20 rings x 60 sectors over 80 m, lidar height 2.0), their ring keys, sector keys and column norms stay in
+ * a database on the device; nothing but the small result record crosses to the host.  Semantics are the restatement of
+ * DESIGN.md (parity unpinned): atanf is modelled as the f64 arctangent rounded to f32, Eigen's reductions follow Eigen
+ * 3.3's SSE2 order, and of ring keys at an equal distance the lower index is the nearer.  Points with a non-finite
+ * coordinate are outside the contract (filter_node removes them) and are skipped.
+ * An ndt_sc is created on a ctx, uses that ctx's device and stream, reports its errors through ndt_last_error(ctx), and is
+ * destroyed before the ctx. */
+typedef struct ndt_sc ndt_sc;
+
+typedef struct {
+    double dist_thres;               /* SC_DIST_THRES (setSCdistThres)                 default 0.2                   */
+    int num_exclude_recent;          /* NUM_EXCLUDE_RECENT                             default 30                    */
+    int num_candidates;              /* NUM_CANDIDATES_FROM_TREE, 1..16                default 3                     */
+    int tree_making_period;          /* TREE_MAKING_PERIOD_ (ndt_sc_detect), >= 1      default 30                    */
+    double search_ratio;             /* SEARCH_RATIO, 0..1 (1 = all 60 shifts)         default 0.1                   */
+} ndt_sc_params;
+
+typedef struct {
+    int loop_id;                     /* nn_idx when min_dist < dist_thres, else -1                                   */
+    float yaw_diff;                  /* deg2rad(nn_align * 6), narrowed through float as the reference does          */
+    double min_dist;                 /* least candidate distance (10000000 when no candidate had one)                */
+    int nn_idx, nn_align;            /* its descriptor and column shift                                              */
+    int n_candidates;                /* ring-key neighbours compared (0: the early return)                           */
+    int cand_idx[16];                /* in ascending ring-key distance; unused slots -1                              */
+    double cand_dist[16];            /* distanceBtnScanContext of the query and each candidate                       */
+    int cand_shift[16];
+} ndt_sc_result;
+
+ndt_status ndt_sc_default_params(ndt_sc_params* out);
+ndt_status ndt_sc_create(ndt_ctx* ctx, const ndt_sc_params* prm, ndt_sc** out);   /* prm NULL = the defaults */
+void ndt_sc_destroy(ndt_sc* sc);
+ndt_status ndt_sc_set_params(ndt_sc* sc, const ndt_sc_params* prm);
+/* descriptors stored (-1 for a NULL handle) */
+int ndt_sc_size(const ndt_sc* sc);
+/* makeAndSaveScancontextAndKeys (:249-260) of a device float4 cloud / of a host cloud (x,y,z at the start of each
+ * stride_bytes record); *index (may be NULL) = the slot it took.  n = 0 stores the all-zero descriptor.  Asynchronous on
+ * the ctx stream: d_xyz4 stays unmodified until the next synchronising call (ndt_sc_detect, ndt_sc_get, ndt_synchronize). */
+ndt_status ndt_sc_add_device(ndt_sc* sc, const float* d_xyz4, size_t n, int* index);
+ndt_status ndt_sc_add(ndt_sc* sc, const float* xyz, size_t n, size_t stride_bytes, int* index);
+/* saveScancontextAndKeys (:236-246): a ready descriptor, column-major 20 x 60 as Eigen stores it. */
+ndt_status ndt_sc_add_descriptor(ndt_sc* sc, const double desc[1200], int* index);
+/* detectLoopClosureID (:331-422) for the newest descriptor.  Stateful like the reference: with fewer than
+ * num_exclude_recent + 1 descriptors it returns the early record (loop_id -1, yaw_diff 0) and leaves the period counter
+ * alone; otherwise the searchable set becomes [0, size - num_exclude_recent) when the counter is a multiple of
+ * tree_making_period, the counter advances, and the search runs in the (possibly stale) set. */
+ndt_status ndt_sc_detect(ndt_sc* sc, ndt_sc_result* out);
+/* Stateless batch form, one launch: query[i] is searched against the ring keys [0, n_search[i]); n_search[i] <= 0 gives
+ * the early record. */
+ndt_status ndt_sc_detect_batch(ndt_sc* sc, const int* query, const int* n_search, int n, ndt_sc_result* out);
+/* distanceBtnScanContext (:116-148) of stored descriptors i and j: the distance and the column shift of j. */
+ndt_status ndt_sc_distance(ndt_sc* sc, int i, int j, double* dist, int* shift);
+/* Read back slot index: the descriptor (1200 doubles, column-major), ring key (20 floats), sector key (60 doubles); any
+ * pointer may be NULL. */
+ndt_status ndt_sc_get(ndt_sc* sc, int index, double* desc, float* ringkey, double* sectorkey);
 
 /* Voxel grid inspection: header = min_b[3], max_b[3], div_b[3], divb_mul[3], n_leaves, n_cloud, overflow,
  * n_valid (16 ints).  Leaves with >= min points (the reference's KD cloud) in ascending key order. */

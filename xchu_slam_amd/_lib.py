@@ -113,6 +113,30 @@ class IcpRecord(C.Structure):
     ]
 
 
+class ScParams(C.Structure):
+    _fields_ = [
+        ("dist_thres", C.c_double),
+        ("num_exclude_recent", C.c_int),
+        ("num_candidates", C.c_int),
+        ("tree_making_period", C.c_int),
+        ("search_ratio", C.c_double),
+    ]
+
+
+class ScResult(C.Structure):
+    _fields_ = [
+        ("loop_id", C.c_int),
+        ("yaw_diff", C.c_float),
+        ("min_dist", C.c_double),
+        ("nn_idx", C.c_int),
+        ("nn_align", C.c_int),
+        ("n_candidates", C.c_int),
+        ("cand_idx", C.c_int * 16),
+        ("cand_dist", C.c_double * 16),
+        ("cand_shift", C.c_int * 16),
+    ]
+
+
 # ndt_icp_state
 ICP_NOT_CONVERGED, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
 
@@ -199,6 +223,18 @@ SIGNATURES = {
     "ndt_icp_align": (C.c_int, [_P, C.POINTER(IcpParams), _FP, C.POINTER(IcpResult)]),
     "ndt_icp_history": (C.c_int, [_P, C.POINTER(IcpRecord), C.c_int, C.POINTER(C.c_int)]),
     "ndt_icp_correspondences": (C.c_int, [_P, C.POINTER(C.c_int), _FP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ndt_sc_default_params": (C.c_int, [C.POINTER(ScParams)]),
+    "ndt_sc_create": (C.c_int, [_P, C.POINTER(ScParams), C.POINTER(_P)]),
+    "ndt_sc_destroy": (None, [_P]),
+    "ndt_sc_set_params": (C.c_int, [_P, C.POINTER(ScParams)]),
+    "ndt_sc_size": (C.c_int, [_P]),
+    "ndt_sc_add_device": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_int)]),
+    "ndt_sc_add": (C.c_int, [_P, _FP, C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]),
+    "ndt_sc_add_descriptor": (C.c_int, [_P, _DP, C.POINTER(C.c_int)]),
+    "ndt_sc_detect": (C.c_int, [_P, C.POINTER(ScResult)]),
+    "ndt_sc_detect_batch": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(ScResult)]),
+    "ndt_sc_distance": (C.c_int, [_P, C.c_int, C.c_int, _DP, C.POINTER(C.c_int)]),
+    "ndt_sc_get": (C.c_int, [_P, C.c_int, _DP, _FP, _DP]),
     "ndt_fitness_score_async_cloud": (C.c_int, [_P, _FP, C.c_double, _P, C.c_size_t]),
     "ndt_fitness_score_async_aligned": (C.c_int, [_P, C.c_double, _P, C.c_size_t]),
     "ndt_keyframe_insert_async": (C.c_int, [_P, _FP, _P, C.c_size_t, C.c_float, _P, C.c_size_t, _P, C.c_size_t]),
@@ -245,7 +281,7 @@ SIGNATURES = {
 
 _lib = None
 # struct layouts this binding mirrors (include/ndt_hip.h NDT_HIP_ABI_VERSION); load() refuses a library built otherwise
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 
 def load() -> C.CDLL:
