@@ -23,9 +23,10 @@ extern "C" {
 /* Layout version of the structs below and of the buffers the library writes through caller pointers
  * (ndt_result, ndt_pass_record, ndt_pair_desc, ndt_filter_params, ndt_pass_phases' 22 doubles).  History: 1 = round 1;
  * 2 = ndt_result.solver_fallbacks appended, ndt_pass_phases 20 -> 22 doubles; 3 = the Scan Context surface (ndt_sc_params,
- * ndt_sc_result; no earlier layout changed).  A caller built against this header checks
+ * ndt_sc_result; no earlier layout changed); 4 = the pose-graph surface (ndt_pgo_params, ndt_pgo_result, ndt_pgo_record;
+ * no earlier layout changed).  A caller built against this header checks
  * ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
-#define NDT_HIP_ABI_VERSION 3
+#define NDT_HIP_ABI_VERSION 4
 
 typedef struct ndt_ctx ndt_ctx;
 
@@ -285,6 +286,64 @@ ndt_status ndt_sc_distance(ndt_sc* sc, int i, int j, double* dist, int* shift);
 /* Read back slot index: the descriptor (1200 doubles, column-major), ring key (20 floats), sector key (60 doubles); any
  * pointer may be NULL. */
 ndt_status ndt_sc_get(ndt_sc* sc, int index, double* desc, float* ringkey, double* sectorkey);
+
+/* ---- Pose graph: what pgo_node asks GTSAM for (pgo_node.cpp:249-291 prior and odometry factors, :453-475 loop factors,
+ * :498-528 ISAM2Update), solved on the device as a batch problem.  The reference holds no GTSAM source, so this is a model
+ * (DESIGN.md "Pose graph", parity unpinned): one SE(3) pose per keyframe in f64, tangent order [wx wy wz vx vy vz],
+ * retraction X <- X Exp(d); a prior on node 0 with residual Log(P^-1 X0); between factors with residual
+ * e = Log(Z^-1 Xi^-1 Xj) (the full SE(3) logarithm, GTSAM's GTSAM_POSE3_EXPMAP chart) whitened by 1/sqrt(var), and an
+ * optional Cauchy kernel (weight k^2 / (k^2 + |e|^2_S), cost k^2/2 log(1 + |e|^2_S / k^2); k = 0: Gaussian).  The result
+ * is a stationary point of the total robust cost, reached by iteratively reweighted Gauss-Newton with exact Jacobians;
+ * iSAM2's estimate differs from it by its relinearisation threshold and the order in which loops arrive.
+ * Poses and measurements are column-major 4 x 4 doubles (as final_tf is) and must be finite rigid transforms.
+ * An ndt_pgo is created on a ctx, uses that ctx's device and stream, reports its errors through ndt_last_error(ctx), and
+ * is destroyed before the ctx. */
+typedef struct ndt_pgo ndt_pgo;
+
+typedef struct {
+    int max_iter;                    /* outer (reweighted Gauss-Newton) iterations, 1..10000   default 200           */
+    double step_eps;                 /* stop when max|d| (rad, m) falls below it               default 1e-10         */
+    int cg_max_iter;                 /* conjugate-gradient iterations per step, 1..10000       default 500           */
+    double cg_rtol;                  /* CG stops at |r| <= cg_rtol |r0| (preconditioned norm)  default 1e-10         */
+    double prior_var[6];             /* priorNoise variances (rotation x 3, translation x 3)   default 1e-12 x 6     */
+    double odom_var[6];              /* odomNoise variances                                    default 1e-6 x 3, 1e-4 x 3 */
+} ndt_pgo_params;
+
+typedef struct {
+    int iterations;                  /* steps taken                                                                  */
+    int converged;                   /* the last step was below step_eps                                             */
+    double cost0, cost;              /* total robust cost at the start / at the returned estimate                    */
+    double max_step;                 /* max|d| of the last step                                                      */
+    int cg_iterations;               /* summed over the steps                                                        */
+} ndt_pgo_result;
+
+typedef struct {
+    double cost;                     /* before the step                                                              */
+    double max_step;
+    int cg_iterations;
+} ndt_pgo_record;
+
+ndt_status ndt_pgo_default_params(ndt_pgo_params* out);
+ndt_status ndt_pgo_create(ndt_ctx* ctx, const ndt_pgo_params* prm, ndt_pgo** out);   /* prm NULL = the defaults */
+void ndt_pgo_destroy(ndt_pgo* pgo);
+/* nodes (-1 for a NULL handle) */
+int ndt_pgo_size(const ndt_pgo* pgo);
+/* A keyframe pose.  Node 0 gets the prior (mean = this pose); every later node gets the odometry edge from its
+ * predecessor, measured between the two poses as given (Run(), :249-291).  The pose is also the node's initial estimate. */
+ndt_status ndt_pgo_add_node(ndt_pgo* pgo, const double pose[16], int* index);
+/* BetweenFactor(i, j, Z) with diagonal variances and a Cauchy kernel of width robust_k (0: none).  i != j, both stored
+ * nodes, either order. */
+ndt_status ndt_pgo_add_between(ndt_pgo* pgo, int i, int j, const double Z[16], const double var[6], double robust_k);
+/* One optimisation, from the current estimate (a call after more nodes or edges is a warm start, as ISAM2Update is); one
+ * launch, synchronises.  A residual rotation within 1e-6 of pi is NDT_EINVAL and a non-finite cost or step NDT_EOVERFLOW;
+ * the estimate is then left as it was. */
+ndt_status ndt_pgo_optimize(ndt_pgo* pgo, ndt_pgo_result* out);
+/* The current estimate: min(cap, size) column-major poses; *n_out (may be NULL) = size. */
+ndt_status ndt_pgo_get_poses(ndt_pgo* pgo, double* poses16, int cap, int* n_out);
+/* The robust weight of every between factor the last optimise held, at its returned estimate, in insertion order. */
+ndt_status ndt_pgo_get_weights(ndt_pgo* pgo, double* w, int cap, int* n_out);
+/* One record per step of the last optimise. */
+ndt_status ndt_pgo_history(ndt_pgo* pgo, ndt_pgo_record* out, int cap, int* n_out);
 
 /* Voxel grid inspection: header = min_b[3], max_b[3], div_b[3], divb_mul[3], n_leaves, n_cloud, overflow,
  * n_valid (16 ints).  Leaves with >= min points (the reference's KD cloud) in ascending key order. */

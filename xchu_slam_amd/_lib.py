@@ -137,6 +137,36 @@ class ScResult(C.Structure):
     ]
 
 
+class PgoParams(C.Structure):
+    _fields_ = [
+        ("max_iter", C.c_int),
+        ("step_eps", C.c_double),
+        ("cg_max_iter", C.c_int),
+        ("cg_rtol", C.c_double),
+        ("prior_var", C.c_double * 6),
+        ("odom_var", C.c_double * 6),
+    ]
+
+
+class PgoResult(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_int),
+        ("converged", C.c_int),
+        ("cost0", C.c_double),
+        ("cost", C.c_double),
+        ("max_step", C.c_double),
+        ("cg_iterations", C.c_int),
+    ]
+
+
+class PgoRecord(C.Structure):
+    _fields_ = [
+        ("cost", C.c_double),
+        ("max_step", C.c_double),
+        ("cg_iterations", C.c_int),
+    ]
+
+
 # ndt_icp_state
 ICP_NOT_CONVERGED, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
 
@@ -235,6 +265,16 @@ SIGNATURES = {
     "ndt_sc_detect_batch": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(ScResult)]),
     "ndt_sc_distance": (C.c_int, [_P, C.c_int, C.c_int, _DP, C.POINTER(C.c_int)]),
     "ndt_sc_get": (C.c_int, [_P, C.c_int, _DP, _FP, _DP]),
+    "ndt_pgo_default_params": (C.c_int, [C.POINTER(PgoParams)]),
+    "ndt_pgo_create": (C.c_int, [_P, C.POINTER(PgoParams), C.POINTER(_P)]),
+    "ndt_pgo_destroy": (None, [_P]),
+    "ndt_pgo_size": (C.c_int, [_P]),
+    "ndt_pgo_add_node": (C.c_int, [_P, _DP, C.POINTER(C.c_int)]),
+    "ndt_pgo_add_between": (C.c_int, [_P, C.c_int, C.c_int, _DP, _DP, C.c_double]),
+    "ndt_pgo_optimize": (C.c_int, [_P, C.POINTER(PgoResult)]),
+    "ndt_pgo_get_poses": (C.c_int, [_P, _DP, C.c_int, C.POINTER(C.c_int)]),
+    "ndt_pgo_get_weights": (C.c_int, [_P, _DP, C.c_int, C.POINTER(C.c_int)]),
+    "ndt_pgo_history": (C.c_int, [_P, C.POINTER(PgoRecord), C.c_int, C.POINTER(C.c_int)]),
     "ndt_fitness_score_async_cloud": (C.c_int, [_P, _FP, C.c_double, _P, C.c_size_t]),
     "ndt_fitness_score_async_aligned": (C.c_int, [_P, C.c_double, _P, C.c_size_t]),
     "ndt_keyframe_insert_async": (C.c_int, [_P, _FP, _P, C.c_size_t, C.c_float, _P, C.c_size_t, _P, C.c_size_t]),
@@ -281,7 +321,7 @@ SIGNATURES = {
 
 _lib = None
 # struct layouts this binding mirrors (include/ndt_hip.h NDT_HIP_ABI_VERSION); load() refuses a library built otherwise
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 def load() -> C.CDLL:

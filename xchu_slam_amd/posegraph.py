@@ -1,0 +1,204 @@
+"""Pose-graph optimisation for pgo_node's loop closures, backed by libndt_hip.so (include/ndt_hip.h, ndt_pgo_*; the
+kernel is csrc/posegraph.hip).
+
+pgo_node turns every keyframe and every accepted loop into a factor of a GTSAM pose graph and ships the optimised
+keyframe poses (pgo_node.cpp:249-291, 453-475, 498-528).  The reference holds no GTSAM source, so this is a model of
+what it asks GTSAM for, solved as a batch problem (DESIGN.md "Pose graph", parity unpinned):
+
+    with xa.PoseGraph() as pg:
+        for p in keyframe_poses: pg.add_node(p)                 # prior on node 0, odometry edges between neighbours
+        for i, j, T, score in accepted: pg.add_loop(i, j, xa.loop_measurement(poses, i, j, T), score)
+        info = pg.optimize()
+        poses6d = pg.poses6d()
+
+`optimize_loops` does exactly that with what `close_loops` returns.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import synth
+from ._lib import PgoParams, PgoRecord, PgoResult, check
+from .ndt import NormalDistributionsTransform, _dp
+
+__all__ = ["PoseGraph", "loop_measurement", "optimize_loops"]
+
+_PARAM_NAMES = tuple(k for k, _ in PgoParams._fields_)
+
+
+def _pose44(pose) -> np.ndarray:
+    p = np.asarray(pose, np.float64)
+    if p.shape == (6,):
+        return synth.pose_matrix(*p)
+    if p.shape != (4, 4):
+        raise ValueError("a pose is a 4 x 4 matrix or (x, y, z, roll, pitch, yaw)")
+    return p
+
+
+def _colmajor(T: np.ndarray) -> np.ndarray:
+    return np.ascontiguousarray(T.T).reshape(-1)
+
+
+def _inv(T: np.ndarray) -> np.ndarray:
+    out = np.eye(4)
+    out[:3, :3] = T[:3, :3].T
+    out[:3, 3] = -T[:3, :3].T @ T[:3, 3]
+    return out
+
+
+class PoseGraph:
+    """The pose graph of pgo_node on MI355X.  It runs on a registration context: its own, or the one of an existing
+    NormalDistributionsTransform (`registration=`), whose device and stream it then shares.  **params are
+    ndt_pgo_params fields: max_iter, step_eps, cg_max_iter, cg_rtol, prior_var, odom_var."""
+
+    def __init__(self, device: int = 0, registration: NormalDistributionsTransform | None = None, **params):
+        self._own = registration is None
+        self._reg = NormalDistributionsTransform(device) if registration is None else registration
+        self._lib = self._reg._lib
+        self._params = PgoParams()
+        check(self._lib.ndt_pgo_default_params(C.byref(self._params)))
+        for k, v in params.items():
+            if k not in _PARAM_NAMES:
+                raise TypeError(f"unknown pose-graph parameter {k!r}")
+            if k in ("prior_var", "odom_var"):
+                v = (C.c_double * 6)(*np.broadcast_to(np.asarray(v, np.float64), (6,)))
+            setattr(self._params, k, v)
+        pg = C.c_void_p()
+        check(self._lib.ndt_pgo_create(self.ctx, C.byref(self._params), C.byref(pg)), self.ctx)
+        self._pg = pg
+
+    # ------------------------------------------------------------------ lifetime
+    def close(self):
+        if getattr(self, "_pg", None):
+            self._lib.ndt_pgo_destroy(self._pg)  # before its context
+            self._pg = None
+        if getattr(self, "_own", False) and self._reg is not None:
+            self._reg.close()
+        self._reg = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def registration(self) -> NormalDistributionsTransform:
+        return self._reg
+
+    @property
+    def ctx(self):
+        return self._reg.ctx
+
+    def __len__(self) -> int:
+        return int(self._lib.ndt_pgo_size(self._pg))
+
+    def params(self) -> dict:
+        return {k: (list(getattr(self._params, k)) if k.endswith("_var") else getattr(self._params, k)) for k in _PARAM_NAMES}
+
+    # ------------------------------------------------------------------ the graph
+    def add_node(self, pose) -> int:
+        """A keyframe pose (4 x 4, or (x, y, z, roll, pitch, yaw) through Pose6D2Matrix).  Node 0 gets the prior, every
+        later node the odometry edge from its predecessor; the pose is the node's initial estimate."""
+        idx = C.c_int()
+        check(self._lib.ndt_pgo_add_node(self._pg, _dp(_colmajor(_pose44(pose))), C.byref(idx)), self.ctx)
+        return idx.value
+
+    def add_loop(self, i: int, j: int, Z, variances, robust_k: float = 1.0):
+        """BetweenFactor(i, j, Z): variances is one number (pgo_node uses the ICP fitness score for all six) or six;
+        robust_k the Cauchy kernel's width (pgo_node: 1; 0: Gaussian)."""
+        var = np.ascontiguousarray(np.broadcast_to(np.asarray(variances, np.float64), (6,)))
+        check(self._lib.ndt_pgo_add_between(self._pg, int(i), int(j), _dp(_colmajor(_pose44(Z))), _dp(var), float(robust_k)), self.ctx)
+
+    def optimize(self) -> dict:
+        """One optimisation from the current estimate (a later call is a warm start)."""
+        r = PgoResult()
+        check(self._lib.ndt_pgo_optimize(self._pg, C.byref(r)), self.ctx)
+        return {"iterations": int(r.iterations), "converged": bool(r.converged), "cost0": float(r.cost0), "cost": float(r.cost),
+                "max_step": float(r.max_step), "cg_iterations": int(r.cg_iterations)}
+
+    def poses(self) -> np.ndarray:
+        """The current estimate, (n, 4, 4) f64."""
+        n = len(self)
+        buf = np.empty(max(1, n) * 16, np.float64)
+        check(self._lib.ndt_pgo_get_poses(self._pg, _dp(buf), n, None), self.ctx)
+        return buf[:n * 16].reshape(n, 4, 4).transpose(0, 2, 1).copy()
+
+    def poses6d(self) -> np.ndarray:
+        """(n, 6) x, y, z, roll, pitch, yaw with the angles as GTSAM's Rot3::rpy gives them, which is what
+        keyframePosesUpdated receives (pgo_node.cpp:517-526)."""
+        T = self.poses()
+        R = T[:, :3, :3]
+        return np.stack([T[:, 0, 3], T[:, 1, 3], T[:, 2, 3], np.arctan2(R[:, 2, 1], R[:, 2, 2]),
+                         np.arctan2(-R[:, 2, 0], np.hypot(R[:, 2, 1], R[:, 2, 2])), np.arctan2(R[:, 1, 0], R[:, 0, 0])], -1)
+
+    def weights(self) -> np.ndarray:
+        """The final robust weight of every loop factor of the last optimize(), in the order they were added."""
+        n = C.c_int()
+        check(self._lib.ndt_pgo_get_weights(self._pg, None, 0, C.byref(n)), self.ctx)
+        buf = np.empty(max(1, n.value), np.float64)
+        check(self._lib.ndt_pgo_get_weights(self._pg, _dp(buf), n.value, None), self.ctx)
+        return buf[:n.value].copy()
+
+    def history(self) -> list[dict]:
+        """Per step of the last optimize(): the cost before it, max|d| and the CG iterations it took."""
+        n = C.c_int()
+        check(self._lib.ndt_pgo_history(self._pg, None, 0, C.byref(n)), self.ctx)
+        buf = (PgoRecord * max(1, n.value))()
+        check(self._lib.ndt_pgo_history(self._pg, buf, n.value, None), self.ctx)
+        return [{"cost": float(buf[i].cost), "max_step": float(buf[i].max_step), "cg_iterations": int(buf[i].cg_iterations)}
+                for i in range(n.value)]
+
+
+def _matrix_to_pose6d(T: np.ndarray):
+    """Matrix2Pose6D (common.h:51-63): tf's getRPY of the rotation."""
+    R = T[:3, :3]
+    if abs(R[2, 0]) >= 1.0:   # gimbal lock: tf's first solution, yaw 0
+        roll, pitch, yaw = math.atan2(R[2, 1], R[2, 2]), math.copysign(math.pi / 2, -R[2, 0]), 0.0
+    else:
+        pitch = -math.asin(R[2, 0])
+        cp = math.cos(pitch)
+        roll = math.atan2(R[2, 1] / cp, R[2, 2] / cp)
+        yaw = math.atan2(R[1, 0] / cp, R[0, 0] / cp)
+    return T[0, 3], T[1, 3], T[2, 3], roll, pitch, yaw
+
+
+def loop_measurement(poses, loop_idx: int, curr_idx: int, T_icp, literal_measurement: bool = False) -> np.ndarray:
+    """The 4 x 4 measurement Z of BetweenFactor(loop_idx, curr_idx, Z) for an ICP result T_icp (host numpy).
+
+    pgo_node's two clouds were already moved into the map frame with the current poses, so T_icp is a correction of
+    the current keyframe's pose, not a relative pose.  The default is the relative pose that correction implies,
+    Z = X_loop^-1 T_icp X_curr.  literal_measurement=True is what the reference adds (pgo_node.cpp:465-473):
+    Z = T_icp^-1 after Matrix2Pose6D / Pose6D2Pose3."""
+    T = np.asarray(T_icp, np.float64)
+    if T.shape != (4, 4):
+        raise ValueError("T_icp is a 4 x 4 matrix")
+    if literal_measurement:
+        return _inv(synth.pose_matrix(*_matrix_to_pose6d(T)))
+    return _inv(_pose44(poses[loop_idx])) @ T @ _pose44(poses[curr_idx])
+
+
+def optimize_loops(poses, accepted, literal_measurement: bool = False, robust_k: float = 1.0, device: int = 0, registration=None,
+                   **params):
+    """pgo_node's back end for a replay: the graph of `poses` (per keyframe a 4 x 4 or (x, y, z, roll, pitch, yaw)) and
+    of `accepted` as close_loops returns it ([(loop_idx, curr_idx, transform, score)]; the score is the loop factor's
+    variance, as pgo_node.cpp:453-457 has it), one optimise.  Returns (poses6d (n, 6), info); info is optimize()'s dict
+    plus "weights" and "poses" (n, 4, 4)."""
+    with PoseGraph(device, registration, **params) as pg:
+        for p in poses:
+            pg.add_node(p)
+        for loop_idx, curr_idx, T, score in accepted:
+            pg.add_loop(loop_idx, curr_idx, loop_measurement(poses, loop_idx, curr_idx, T, literal_measurement), score, robust_k)
+        info = pg.optimize()
+        info["weights"] = pg.weights()
+        info["poses"] = pg.poses()
+        return pg.poses6d(), info
