@@ -24,9 +24,9 @@ extern "C" {
  * (ndt_result, ndt_pass_record, ndt_pair_desc, ndt_filter_params, ndt_pass_phases' 22 doubles).  History: 1 = round 1;
  * 2 = ndt_result.solver_fallbacks appended, ndt_pass_phases 20 -> 22 doubles; 3 = the Scan Context surface (ndt_sc_params,
  * ndt_sc_result; no earlier layout changed); 4 = the pose-graph surface (ndt_pgo_params, ndt_pgo_result, ndt_pgo_record;
- * no earlier layout changed).  A caller built against this header checks
- * ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
-#define NDT_HIP_ABI_VERSION 4
+ * no earlier layout changed); 5 = the ISC surface (ndt_isc_params, ndt_isc_result); no earlier layout changed.  A caller
+ * built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
+#define NDT_HIP_ABI_VERSION 5
 
 typedef struct ndt_ctx ndt_ctx;
 
@@ -286,6 +286,73 @@ ndt_status ndt_sc_distance(ndt_sc* sc, int i, int j, double* dist, int* shift);
 /* Read back slot index: the descriptor (1200 doubles, column-major), ring key (20 floats), sector key (60 doubles); any
  * pointer may be NULL. */
 ndt_status ndt_sc_get(ndt_sc* sc, int index, double* desc, float* ringkey, double* sectorkey);
+
+/* ---- Intensity Scan Context: ISCGeneration (xchu_mapping/include/isc/ISCGeneration.{h,cpp}), pgo_node's loop_method 2
+ * (makeAndSavedec per keyframe at pgo_node.cpp:239, detectLoopClosureID at :366).  A descriptor is a rings x sectors matrix
+ * of bytes (the largest (int)(255 * intensity) of the points of each polar cell, -0.9 <= z <= 30); the database (the
+ * descriptors sector-major, per column the ring masks "cell == 0" and "cell == 1", the keyframe positions and travel
+ * distances) stays on the device and nothing but the small result record crosses to the host.  Semantics are the
+ * restatement of DESIGN.md §2 "ISC" (parity unpinned): atan2f is modelled as the f64 arctangent rounded to f32; three
+ * deviations, each where the reference leaves its row or depends on point order: a negative sector index (y = -0, x < 0)
+ * is skipped, an intensity outside 0..1 clamps to 0..255 (NaN: 0), and the intensity window wraps its column with a true
+ * modulo.  Everything after the binning is integer arithmetic and f64 quotients of integers: bit-exact.
+ * An ndt_isc is created on a ctx, uses that ctx's device and stream, reports its errors through ndt_last_error(ctx), and is
+ * destroyed before the ctx. */
+typedef struct ndt_isc ndt_isc;
+
+typedef struct {
+    int rings;                       /* init_param, 1..64                              pgo_node: 60                  */
+    int sectors;                     /* init_param, 20..128                            pgo_node: 60                  */
+    double max_dis;                  /* init_param, > 0                                pgo_node: 40.0                */
+    double skip_neighbour_distance;  /* SKIP_NEIBOUR_DISTANCE                          20.0                          */
+    double inflation_covariance;     /* INFLATION_COVARIANCE                           0.03                          */
+    double geometry_threshold;       /* GEOMETRY_THRESHOLD                             0.67                          */
+    double intensity_threshold;      /* INTENSITY_THRESHOLD                            0.91                          */
+    float z_min, z_max;              /* ground_filter's PassThrough limits, inclusive  -0.9, 30.0                    */
+} ndt_isc_params;
+
+typedef struct {
+    int loop_id;                     /* prev, or -1 (also whenever the winning index is 0, as the reference)         */
+    int curr_id;                     /* the query index                                                              */
+    int best_id;                     /* the winning index before the "!= 0" rule; 0 when none                        */
+    double best_score;               /* geo_score + inten_score of the winner (0 when none)                          */
+    double geo_score, inten_score;
+    int angle;                       /* the winner's column shift                                                    */
+    int n_gated;                     /* pairs that passed the travel / position gate                                 */
+    int n_geometry;                  /* of those, past the geometry threshold                                        */
+    int n_loop_pairs;                /* of those, past the intensity threshold too                                   */
+} ndt_isc_result;
+
+/* pgo_node's init_param values and the five #defines of ISCGeneration.h */
+ndt_status ndt_isc_default_params(ndt_isc_params* out);
+/* prm NULL = the defaults.  The parameters are fixed at creation: the database layout depends on them. */
+ndt_status ndt_isc_create(ndt_ctx* ctx, const ndt_isc_params* prm, ndt_isc** out);
+void ndt_isc_destroy(ndt_isc* isc);
+/* descriptors stored (-1 for a NULL handle) */
+int ndt_isc_size(const ndt_isc* isc);
+/* makeAndSavedec (:195-214) of a device float4 x,y,z,intensity cloud / of a host cloud (x,y,z at the start of each
+ * stride_bytes record, intensity at float index intensity_offset); pos = the keyframe position as given (pgo_node passes
+ * z = 0), narrowed through f32 as pcl::PointXYZI holds it; *index (may be NULL) = the slot it took.  n = 0 stores the
+ * all-zero descriptor.  Asynchronous on the ctx stream: d_xyzi4 stays unmodified until the next synchronising call
+ * (ndt_isc_detect, ndt_isc_get, ndt_synchronize). */
+ndt_status ndt_isc_add_device(ndt_isc* isc, const float* d_xyzi4, size_t n, const double pos[3], int* index);
+ndt_status ndt_isc_add(ndt_isc* isc, const float* xyzi, size_t n, size_t stride_bytes, int intensity_offset, const double pos[3],
+                       int* index);
+/* A ready descriptor, row-major rings x sectors bytes. */
+ndt_status ndt_isc_add_descriptor(ndt_isc* isc, const unsigned char* bytes, const double pos[3], int* index);
+/* detectLoopClosureID (:157-193) for the newest keyframe. */
+ndt_status ndt_isc_detect(ndt_isc* isc, ndt_isc_result* out);
+/* Stateless batch form, one submission: query[k] is tested as if it were the newest keyframe (only indices <= query[k],
+ * with its own travel distance, take part). */
+ndt_status ndt_isc_detect_batch(ndt_isc* isc, const int* query, int n, ndt_isc_result* out);
+/* is_loop_pair (:216-229) of stored descriptors i (desc1) and j (desc2): the geometry score and its column shift, the
+ * intensity score (computed whatever the geometry score is) and the reference's verdict.  Any pointer may be NULL. */
+ndt_status ndt_isc_pair(ndt_isc* isc, int i, int j, double* geo, int* angle, double* inten, int* is_loop);
+/* calculate_intensity_dis (:259-283) of stored descriptors i and j around a given column shift, 0 <= angle < sectors. */
+ndt_status ndt_isc_intensity(ndt_isc* isc, int i, int j, int angle, double* inten);
+/* Read back slot index: the descriptor (row-major rings x sectors bytes), the position (3 doubles), the travel distance;
+ * any pointer may be NULL. */
+ndt_status ndt_isc_get(ndt_isc* isc, int index, unsigned char* bytes, double* pos, double* travel);
 
 /* ---- Pose graph: what pgo_node asks GTSAM for (pgo_node.cpp:249-291 prior and odometry factors, :453-475 loop factors,
  * :498-528 ISAM2Update), solved on the device as a batch problem.  The reference holds no GTSAM source, so this is a model

@@ -137,6 +137,35 @@ class ScResult(C.Structure):
     ]
 
 
+class IscParams(C.Structure):
+    _fields_ = [
+        ("rings", C.c_int),
+        ("sectors", C.c_int),
+        ("max_dis", C.c_double),
+        ("skip_neighbour_distance", C.c_double),
+        ("inflation_covariance", C.c_double),
+        ("geometry_threshold", C.c_double),
+        ("intensity_threshold", C.c_double),
+        ("z_min", C.c_float),
+        ("z_max", C.c_float),
+    ]
+
+
+class IscResult(C.Structure):
+    _fields_ = [
+        ("loop_id", C.c_int),
+        ("curr_id", C.c_int),
+        ("best_id", C.c_int),
+        ("best_score", C.c_double),
+        ("geo_score", C.c_double),
+        ("inten_score", C.c_double),
+        ("angle", C.c_int),
+        ("n_gated", C.c_int),
+        ("n_geometry", C.c_int),
+        ("n_loop_pairs", C.c_int),
+    ]
+
+
 class PgoParams(C.Structure):
     _fields_ = [
         ("max_iter", C.c_int),
@@ -265,6 +294,18 @@ SIGNATURES = {
     "ndt_sc_detect_batch": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(ScResult)]),
     "ndt_sc_distance": (C.c_int, [_P, C.c_int, C.c_int, _DP, C.POINTER(C.c_int)]),
     "ndt_sc_get": (C.c_int, [_P, C.c_int, _DP, _FP, _DP]),
+    "ndt_isc_default_params": (C.c_int, [C.POINTER(IscParams)]),
+    "ndt_isc_create": (C.c_int, [_P, C.POINTER(IscParams), C.POINTER(_P)]),
+    "ndt_isc_destroy": (None, [_P]),
+    "ndt_isc_size": (C.c_int, [_P]),
+    "ndt_isc_add_device": (C.c_int, [_P, _P, C.c_size_t, _DP, C.POINTER(C.c_int)]),
+    "ndt_isc_add": (C.c_int, [_P, _FP, C.c_size_t, C.c_size_t, C.c_int, _DP, C.POINTER(C.c_int)]),
+    "ndt_isc_add_descriptor": (C.c_int, [_P, C.POINTER(C.c_ubyte), _DP, C.POINTER(C.c_int)]),
+    "ndt_isc_detect": (C.c_int, [_P, C.POINTER(IscResult)]),
+    "ndt_isc_detect_batch": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(IscResult)]),
+    "ndt_isc_pair": (C.c_int, [_P, C.c_int, C.c_int, _DP, C.POINTER(C.c_int), _DP, C.POINTER(C.c_int)]),
+    "ndt_isc_intensity": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
+    "ndt_isc_get": (C.c_int, [_P, C.c_int, C.POINTER(C.c_ubyte), _DP, _DP]),
     "ndt_pgo_default_params": (C.c_int, [C.POINTER(PgoParams)]),
     "ndt_pgo_create": (C.c_int, [_P, C.POINTER(PgoParams), C.POINTER(_P)]),
     "ndt_pgo_destroy": (None, [_P]),
@@ -321,7 +362,7 @@ SIGNATURES = {
 
 _lib = None
 # struct layouts this binding mirrors (include/ndt_hip.h NDT_HIP_ABI_VERSION); load() refuses a library built otherwise
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 def load() -> C.CDLL:

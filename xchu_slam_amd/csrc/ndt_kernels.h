@@ -7,6 +7,7 @@
 #include "ndt_linalg.h"
 #include "ndt_icp.h"
 #include "ndt_sc.h"
+#include "ndt_isc.h"
 #include "ndt_pgo.h"
 
 namespace ndt {
@@ -42,6 +43,10 @@ __global__ void k_icp_pass(float4*, int, IcpState*, const GridHeader*, const int
 __global__ void k_sc_make(const float4*, int, unsigned*);
 __global__ void k_sc_finalize(const unsigned*, ScDb, int);
 __global__ void k_sc_detect(ScDb, const int*, const int*, int, int, ScDetectArgs, ndt_sc_result*);
+__global__ void k_isc_make(const float4*, int, IscGeom, unsigned*);
+__global__ void k_isc_finalize(const unsigned*, IscDb, int, int, int, double, double, double, double);
+__global__ void k_isc_detect(IscDb, const int*, int, IscDetectArgs, IscPartial*);
+__global__ void k_isc_reduce(const IscPartial*, const int*, int, int, IscDetectArgs, ndt_isc_result*);
 __global__ void k_pgo_optimize(PgoGraph, PgoArgs);
 __global__ void k_fit_block_flags(const int*, const GridHeader*, int*);
 __global__ void k_append2(const float4*, const float4*, int, const GridHeader*, float4*, float4*);

@@ -20,6 +20,7 @@ import numpy as np
 
 from ._lib import ScParams, ScResult, check
 from .icp import refine_loop
+from .isc import detect_loops_isc
 from .ndt import NormalDistributionsTransform, _dp, _fp, as_points
 
 __all__ = ["SCManager", "detect_loops", "close_loops", "search_schedule"]
@@ -209,10 +210,15 @@ def detect_loops(keyframes=None, tree_making_period: int = 1, device: int = 0, r
         return sc.detect_batch(np.arange(n), sched)
 
 
-def close_loops(keyframes, poses, max_pair_dist: float = 20.0, detect_args: dict | None = None, **refine_args):
+def close_loops(keyframes, poses, max_pair_dist: float = 20.0, detect_args: dict | None = None, loop_method: int = 1,
+                **refine_args):
     """pgo_node's loop-closure path for a whole replay: detect_loops, PerformSCLoopClosure's gate (pgo_node.cpp:351-362:
     the planar distance between the two keyframe poses must not exceed 20 m), then refine_loop (PGO::ICPRefine) for each
     surviving pair.  keyframes: (N, 4) x,y,z,intensity clouds; poses: per keyframe (x, y, z, roll, pitch, yaw).
+
+    loop_method is pgo_node's switch: 1 (default) detects with Scan Context, 2 with Intensity Scan Context
+    (detect_loops_isc, which reads the keyframes' fourth column; the same gate follows, pgo_node.cpp:373-384), and
+    detect_args then holds detect_loops_isc's keywords (device and IscParams fields).
 
     Two sets of settings go in, kept apart because both callees take keyword settings of their own:
     detect_args: a dict handed to detect_loops as keywords — tree_making_period, device, and the detector's dist_thres,
@@ -224,7 +230,12 @@ def close_loops(keyframes, poses, max_pair_dist: float = 20.0, detect_args: dict
     [(loop_idx, curr_idx, reason)] with reason "pair_distance" or "icp"."""
     if len(poses) != len(keyframes):
         raise ValueError("poses do not match keyframes")
-    records = detect_loops([np.asarray(k)[:, :3] for k in keyframes], **(detect_args or {}))
+    if loop_method == 1:
+        records = detect_loops([np.asarray(k)[:, :3] for k in keyframes], **(detect_args or {}))
+    elif loop_method == 2:
+        records = detect_loops_isc(keyframes, poses, **(detect_args or {}))
+    else:
+        raise ValueError("loop_method is 1 (Scan Context) or 2 (Intensity Scan Context)")
     accepted, rejected = [], []
     for curr, rec in enumerate(records):
         prev = rec["loop_id"]
