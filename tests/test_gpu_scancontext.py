@@ -132,6 +132,33 @@ def test_descriptor_and_keys():
         assert sc.distanceBtnScanContext(k, k - 1) == R.distance(full, full)
 
 
+def test_database_growth(route):
+    """70 adds cross the first growth step (64 slots): every earlier slot reads back as before."""
+    import xchu_slam_amd as xa
+    scan = route["scans"][50]
+    parts = [scan[40 * k: 40 * k + 40] for k in range(70)]
+    refs = [R.make_scancontext(p) for p in parts]
+    with xa.SCManager() as sc:
+        for k, p in enumerate(parts):
+            if k % 7 == 3:
+                sc.saveScancontextAndKeys(refs[k])
+            else:
+                sc.makeAndSaveScancontextAndKeys(p)
+            if k == 63:
+                before = [sc._get(s) for s in range(64)]
+        assert len(sc) == 70
+        for s in range(70):
+            got = sc._get(s)
+            for a, b in zip(got, (refs[s], R.ring_key(refs[s]), R.sector_key(refs[s]))):
+                assert same_bits(a, b), s
+            assert s >= 64 or all(same_bits(a, b) for a, b in zip(got, before[s])), s
+        # the column norms moved too: a pair on each side of the growth step and one across it
+        for i, j in ((5, 20), (66, 69), (69, 5)):
+            dist, shift = sc.distanceBtnScanContext(i, j)
+            rd, rs = R.distance(refs[i], refs[j])
+            assert same_bits(np.float64(dist), np.float64(rd)) and shift == rs, (i, j, dist, shift, rd, rs)
+
+
 # ---------------------------------------------------------------------------------------------- distanceBtnScanContext
 def test_distance_pairs(route):
     import xchu_slam_amd as xa

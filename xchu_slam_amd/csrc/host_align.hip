@@ -8,11 +8,8 @@ namespace ndt::host {
 void invalidate_graph(ndt_ctx* c) {
     bool any = false;
     for (auto& g : c->graphs) any = any || g.exec;
-    if (any && c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& g : c->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        g.exec = nullptr;
-    }
+    if (any && c->stream) (void)hipStreamSynchronize(c->stream.get());
+    for (auto& g : c->graphs) g.exec.reset();
 }
 
 // Device copy on `stream` by k_copy16 when both pointers and the size are 16-byte aligned, else a runtime copy
@@ -34,31 +31,30 @@ ndt_status flush_source(ndt_ctx* c) {
     if (!c->src_pend) return NDT_OK;
     const float4* p = c->src_pend;
     c->src_pend = nullptr;
-    if (c->N) TRY(copy16(c, c->stream, c->source.p, p, (size_t)c->N * sizeof(float4)));
+    if (c->N) TRY(copy16(c, c->stream.get(), c->source.p, p, (size_t)c->N * sizeof(float4)));
     return NDT_OK;
 }
 
 // One graph from what `body` queues on the ctx stream: captured under capture_mu (see ndt_ctx), instantiated into *out
-// (nullptr on failure).  end_what prefixes the error text of a capture the runtime rejects.
-ndt_status capture_graph(ndt_ctx* c, const char* end_what, const std::function<ndt_status()>& body, hipGraphExec_t* out) {
-    *out = nullptr;
+// (empty on failure).  end_what prefixes the error text of a capture the runtime rejects.
+ndt_status capture_graph(ndt_ctx* c, const char* end_what, const std::function<ndt_status()>& body, GraphExec* out) {
+    out->reset();
     hipGraph_t g = nullptr;
     std::unique_lock<std::shared_mutex> capture(c->capture_mu);
-    HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    HIPCHK(c, hipStreamBeginCapture(c->stream.get(), hipStreamCaptureModeThreadLocal));
     const ndt_status st = body();
-    hipError_t e = hipStreamEndCapture(c->stream, &g);
+    hipError_t e = hipStreamEndCapture(c->stream.get(), &g);
     capture.unlock();
     if (st != NDT_OK) {
         if (e == hipSuccess) (void)hipGraphDestroy(g);
         return st;
     }
     if (e != hipSuccess) return fail(c, NDT_EDEVICE, std::string(end_what) + hipGetErrorString(e));
-    e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    hipGraphExec_t gx = nullptr;
+    e = hipGraphInstantiate(&gx, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
-    if (e != hipSuccess) {
-        *out = nullptr;
-        return fail(c, NDT_EDEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(c, NDT_EDEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+    out->reset(gx);
     return NDT_OK;
 }
 
@@ -98,7 +94,7 @@ int direct_blocks(const ndt_ctx* c, bool lead, int n, int ppt, bool one_tile = f
 // summed by the two-level hand-off (pass_handoff); the alternative to the two-points-per-thread tile loop (pass_ppt2).
 // ndt_set_pass_options(points_per_thread = 3) selects it (A/B; off by default).
 bool grid_one_tile(const ndt_ctx* c) {
-    if (c->opt_ppt != 3 || c->prm.search == NDT_DIRECT26) return false;
+    if (c->opt.ppt != 3 || c->prm.search == NDT_DIRECT26) return false;
     return geom_points(std::max(1, c->N)) > c->n_cu * kLeadBlock1;
 }
 
@@ -107,7 +103,7 @@ bool grid_one_tile(const ndt_ctx* c) {
 // scans: pass 87 -> 81 us; at C4's 3 tiles the halved tile count loses, 27.4 -> 28.8 us).  Every cloud index must then
 // fit 22 bits.  ndt_set_pass_options(points_per_thread = 1) keeps one point per thread.
 bool pass_ppt2(const ndt_ctx* c) {
-    if (c->opt_ppt != 2 || c->prm.search == NDT_DIRECT26 || grid_one_tile(c)) return false;
+    if (c->opt.ppt != 2 || c->prm.search == NDT_DIRECT26 || grid_one_tile(c)) return false;
     const long long max_cloud = (long long)c->M / std::max(1, c->prm.min_points_per_voxel) + 1;
     const int n = geom_points(std::max(1, c->N));
     const int rounds1 = ceil_div(n, direct_blocks(c, false, n, 1) * pass_block(c->prm.search, false));
@@ -175,17 +171,17 @@ void launch_pass(ndt_ctx* c, int mode) {
                  : p.search == NDT_DIRECT1
                      ? (ppt2 ? k_pass_direct<S_DIRECT1, 2, false> : (one ? k_pass_direct<S_DIRECT1, 1, true> : k_pass_direct<S_DIRECT1, 1, false>))
                      : (ppt2 ? k_pass_direct<S_DIRECT7, 2, false> : (one ? k_pass_direct<S_DIRECT7, 1, true> : k_pass_direct<S_DIRECT7, 1, false>));
-    hipLaunchKernelGGL(kern, dim3(g.nb), dim3(g.block), 0, c->stream, c->pass_src, geom_points(c->N), g.ppb, c->d_hdr,
-                       c->table.p, c->grid.p, c->recs.p, c->d_state, c->d_state, c->partials.p, c->counter.p, c->reduce_out.p,
-                       c->d_hist, c->hist_cap, mode, c->profiling ? c->ts.p : nullptr, nbr_cache(c, mode));
+    hipLaunchKernelGGL(kern, dim3(g.nb), dim3(g.block), 0, c->stream.get(), c->pass_src, geom_points(c->N), g.ppb, c->d_hdr.p,
+                       c->table.p, c->grid.p, c->recs.p, c->d_state.p, c->d_state.p, c->partials.p, c->counter.p, c->reduce_out.p,
+                       c->d_hist.p, c->hist_cap, mode, c->opt.profiling ? c->prof.ts.p : nullptr, nbr_cache(c, mode));
 }
 
 void launch_radius(ndt_ctx* c, int mode) {
     const int nb = pass_blocks(geom_points(c->N));
-    hipLaunchKernelGGL(k_pass_radius, dim3(nb), dim3(kBlock), 0, c->stream, c->pass_src, geom_points(c->N), c->d_hdr, c->table.p, c->grid.p, c->recs.p,
-                       c->cent.p, c->icovd.p, c->d_state, c->d_state, c->partials.p, c->counter.p, c->reduce_out.p, c->d_hist,
+    hipLaunchKernelGGL(k_pass_radius, dim3(nb), dim3(kBlock), 0, c->stream.get(), c->pass_src, geom_points(c->N), c->d_hdr.p, c->table.p, c->grid.p, c->recs.p,
+                       c->cent.p, c->icovd.p, c->d_state.p, c->d_state.p, c->partials.p, c->counter.p, c->reduce_out.p, c->d_hist.p,
                        c->hist_cap, mode,
-                       c->profiling ? c->ts.p : nullptr);
+                       c->opt.profiling ? c->prof.ts.p : nullptr);
 }
 
 // One leading-tail pass kernel (k_pass_lead) as kernel j = c->lead_par of the align's chain (see ndt_ctx::lead); the
@@ -193,31 +189,29 @@ void launch_radius(ndt_ctx* c, int mode) {
 void launch_lead(ndt_ctx* c, int j) {
     const PassGeom g = direct_geom(c, true);
     const bool one = lead_one_tile(c);
-    AlignState* st[2] = {c->d_state, c->d_state2};
+    AlignState* st[2] = {c->d_state.p, c->d_state2.p};
     double* pp[2] = {c->partials.p, c->partials2.p};
     const AlignState* sin = st[j & 1];
     AlignState* sout = st[(j + 1) & 1];
     const double* pin = pp[(j + 1) & 1];
     double* pout = pp[j & 1];
-    unsigned long long* ts = c->profiling ? c->ts.p : nullptr;
+    unsigned long long* ts = c->opt.profiling ? c->prof.ts.p : nullptr;
     auto* kern = c->prm.search == NDT_DIRECT26  ? k_pass_lead<S_DIRECT26, false>
                  : c->prm.search == NDT_DIRECT1 ? (one ? k_pass_lead<S_DIRECT1, true> : k_pass_lead<S_DIRECT1, false>)
                                                 : (one ? k_pass_lead<S_DIRECT7, true> : k_pass_lead<S_DIRECT7, false>);
-    hipLaunchKernelGGL(kern, dim3(g.nb), dim3(g.block), 0, c->stream, c->pass_src, geom_points(c->N), g.ppb, c->d_hdr, c->table.p,
-                       c->grid.p, c->recs.p, sin, sout, pin, pout, c->d_hist, c->hist_cap, ts, nbr_cache(c, 0));
+    hipLaunchKernelGGL(kern, dim3(g.nb), dim3(g.block), 0, c->stream.get(), c->pass_src, geom_points(c->N), g.ppb, c->d_hdr.p, c->table.p,
+                       c->grid.p, c->recs.p, sin, sout, pin, pout, c->d_hist.p, c->hist_cap, ts, nbr_cache(c, 0));
 }
 
-// enqueue `slots` (pass, control) pairs; pass events optional
-ndt_status enqueue_chain(ndt_ctx* c, int slots, bool mt_possible, bool with_events) {
+// enqueue `slots` (pass, control) pairs
+ndt_status enqueue_chain(ndt_ctx* c, int slots, bool mt_possible) {
     for (int s = 0; s < slots; ++s) {
-        if (with_events) HIPCHK(c, hipEventRecord(c->pass_ev[2 * s], c->stream));
         if (c->lead) {
             launch_lead(c, c->lead_par + s);
         } else {
             launch_pass(c, 0);
             if (needs_radius(c->prm, mt_possible)) launch_radius(c, 0);
         }
-        if (with_events) HIPCHK(c, hipEventRecord(c->pass_ev[2 * s + 1], c->stream));
     }
     HIPCHK(c, hipGetLastError());
     return NDT_OK;
@@ -275,21 +269,11 @@ ndt_status ensure_align_buffers(ndt_ctx* c) {
     return NDT_OK;
 }
 
-ndt_status ensure_pass_events(ndt_ctx* c, int slots) {
-    if ((int)c->pass_ev.size() < 2 * slots) {
-        size_t old = c->pass_ev.size();
-        c->pass_ev.resize(2 * slots);
-        for (size_t k = old; k < c->pass_ev.size(); ++k) HIPCHK(c, hipEventCreate(&c->pass_ev[k]));
-        invalidate_graph(c);
-    }
-    return NDT_OK;
-}
-
 // The device state after `ahead` more kernels of the chain: the only state buffer without leading-tail chains, else
 // the ping-pong buffer kernel lead_par + ahead reads.
 AlignState* lead_state(ndt_ctx* c, int ahead) {
-    if (!c->lead) return c->d_state;
-    return ((c->lead_par + ahead) & 1) ? c->d_state2 : c->d_state;
+    if (!c->lead) return c->d_state.p;
+    return ((c->lead_par + ahead) & 1) ? c->d_state2.p : c->d_state.p;
 }
 
 // End-of-round read-back, queued on the stream before the align's own synchronisation (no extra round trip): the
@@ -297,17 +281,14 @@ AlignState* lead_state(ndt_ctx* c, int ahead) {
 // straight into pinned host memory (blit copies would cost a launch + gap each), then the round's sequence number.
 ndt_status prepare_readback(ndt_ctx* c, int from, int to) {
     to = std::min(to, c->hist_cap);
-    const bool prof = c->profiling && to > from;
-    if (prof && c->h_prof_cap < c->hist_cap) {
-        if (c->h_ts) (void)hipHostFree(c->h_ts);
-        if (c->h_hist) (void)hipHostFree(c->h_hist);
-        c->h_ts = nullptr;
-        c->h_hist = nullptr;
-        c->h_prof_cap = 0;
-        if (hipHostMalloc(&c->h_ts, kTsStride * (size_t)c->hist_cap * sizeof(unsigned long long), hipHostMallocCoherent) != hipSuccess ||
-            hipHostMalloc(&c->h_hist, (size_t)c->hist_cap * sizeof(PassRecordDev), hipHostMallocCoherent) != hipSuccess)
-            return fail(c, NDT_ENOMEM, "hipHostMalloc failed");
-        c->h_prof_cap = c->hist_cap;
+    const bool prof = c->opt.profiling && to > from;
+    if (prof && !c->prof.h_ts) {  // both blocks or neither (hist_cap is fixed: made once)
+        Pinned<unsigned long long[]> h_ts;
+        Pinned<PassRecordDev[]> h_hist;
+        TRY(make_pinned(c, h_ts, kTsStride * (size_t)c->hist_cap, hipHostMallocCoherent));
+        TRY(make_pinned(c, h_hist, (size_t)c->hist_cap, hipHostMallocCoherent));
+        c->prof.h_hist = std::move(h_hist);
+        c->prof.h_ts = std::move(h_ts);
     }
     return NDT_OK;
 }
@@ -315,19 +296,19 @@ ndt_status prepare_readback(ndt_ctx* c, int from, int to) {
 // seq: the round's sequence number, or 0 for the one k_align_init stored in d_clk[2] (the launch is then graph-capturable)
 void launch_readback(ndt_ctx* c, int from, int to, const AlignState* d_src, unsigned long long seq) {
     to = std::min(to, c->hist_cap);
-    const bool prof = c->profiling && to > from;
+    const bool prof = c->opt.profiling && to > from;
     static_assert(sizeof(PassRecordDev) % 8 == 0, "pass records copied as 8-byte words");
     using u64 = unsigned long long;
     const int ts_words = prof ? kTsStride * (to - from) : 0;
     const int hist_words = prof ? (int)((to - from) * sizeof(PassRecordDev) / 8) : 0;
-    const u64* ts = prof ? c->ts.p + kTsStride * (size_t)from : nullptr;
-    u64* h_ts = prof ? c->h_ts + kTsStride * (size_t)from : nullptr;
-    const u64* hist = prof ? reinterpret_cast<const u64*>(c->d_hist + from) : nullptr;
-    u64* h_hist = prof ? reinterpret_cast<u64*>(c->h_hist + from) : nullptr;
-    hipLaunchKernelGGL(k_readback, dim3(1), dim3(kBlock), 0, c->stream, reinterpret_cast<const u64*>(d_src),
-                       reinterpret_cast<u64*>(c->h_state), (int)(sizeof(AlignState) / 8), ts, h_ts, ts_words, hist, h_hist, hist_words,
-                       c->d_clk, c->h_rb + 1, c->h_rb, seq,
-                       d_src != c->d_state ? reinterpret_cast<u64*>(c->d_state) : nullptr, c->d_hdr);
+    const u64* ts = prof ? c->prof.ts.p + kTsStride * (size_t)from : nullptr;
+    u64* h_ts = prof ? c->prof.h_ts.get() + kTsStride * (size_t)from : nullptr;
+    const u64* hist = prof ? reinterpret_cast<const u64*>(c->d_hist.p + from) : nullptr;
+    u64* h_hist = prof ? reinterpret_cast<u64*>(c->prof.h_hist.get() + from) : nullptr;
+    hipLaunchKernelGGL(k_readback, dim3(1), dim3(kBlock), 0, c->stream.get(), reinterpret_cast<const u64*>(d_src),
+                       reinterpret_cast<u64*>(c->h_state.get()), (int)(sizeof(AlignState) / 8), ts, h_ts, ts_words, hist, h_hist, hist_words,
+                       c->d_clk.p, c->h_rb.get() + 1, c->h_rb.get(), seq,
+                       d_src != c->d_state.p ? reinterpret_cast<u64*>(c->d_state.p) : nullptr, c->d_hdr.p);
 }
 
 // with_readback: the round's k_readback is captured as the graph's last node (the first round of an align: from 0 to
@@ -339,19 +320,19 @@ ndt_status build_graph(ndt_ctx* c, int slots, bool mt_possible, hipGraphExec_t* 
     // (one slot per captured pointer: a combined key could collide after a reallocation and replay freed buffers)
     const long long key[kGraphKey] = {geom_points(c->N), (long long)(uintptr_t)c->pass_src, (long long)(uintptr_t)c->table.p, c->prm.search,
                                       c->prm.precision_mode,
-                                      mt_possible | (c->profiling ? 2 : 0) | (c->lead ? 4 : 0) | ((c->lead_par & 1) ? 8 : 0) |
+                                      mt_possible | (c->opt.profiling ? 2 : 0) | (c->lead ? 4 : 0) | ((c->lead_par & 1) ? 8 : 0) |
                                           (pass_ppt2(c) ? 16 : 0), slots,
                                       (long long)(uintptr_t)c->recs.p, (long long)(uintptr_t)c->partials.p,
                                       (long long)(uintptr_t)c->grid.p, (long long)(uintptr_t)c->reduce_out.p,
                                       (long long)(uintptr_t)c->counter.p, (long long)(uintptr_t)c->cent.p,
-                                      (long long)(uintptr_t)c->icovd.p, (long long)(uintptr_t)c->ts.p,
-                                      (long long)(uintptr_t)c->d_hdr, (long long)(uintptr_t)c->d_state,
-                                      (long long)(uintptr_t)c->d_hist, (long long)(uintptr_t)c->partials2.p,
+                                      (long long)(uintptr_t)c->icovd.p, (long long)(uintptr_t)c->prof.ts.p,
+                                      (long long)(uintptr_t)c->d_hdr.p, (long long)(uintptr_t)c->d_state.p,
+                                      (long long)(uintptr_t)c->d_hist.p, (long long)(uintptr_t)c->partials2.p,
                                       (long long)(uintptr_t)nbr_cache(c, 0), with_readback ? 1 : 0,
-                                      (long long)(uintptr_t)c->h_ts, (long long)(uintptr_t)c->h_hist};
+                                      (long long)(uintptr_t)c->prof.h_ts.get(), (long long)(uintptr_t)c->prof.h_hist.get()};
     for (auto& g : c->graphs)
         if (g.exec && std::memcmp(key, g.key, sizeof(key)) == 0) {
-            *out = g.exec;
+            *out = g.exec.get();
             return NDT_OK;
         }
     ndt_ctx::GraphEntry& slot = c->graphs[c->graph_next];
@@ -359,20 +340,19 @@ ndt_status build_graph(ndt_ctx* c, int slots, bool mt_possible, hipGraphExec_t* 
     if (slot.exec) {
         // the evicted chain may still run on the stream (an earlier align of this ctx, an async align whose wait has not
         // come): its executable owns the kernel arguments of its nodes, so it is destroyed only once the stream is past it
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipGraphExecDestroy(slot.exec);
+        HIPCHK(c, hipStreamSynchronize(c->stream.get()));
+        slot.exec.reset();
     }
-    slot.exec = nullptr;
-    if (c->profiling) TRY(ensure(c, c->ts, kTsStride * (size_t)c->hist_cap));
+    if (c->opt.profiling) TRY(ensure(c, c->prof.ts, kTsStride * (size_t)c->hist_cap));
     const int rb_to = slots * (mt_possible ? 4 : 1);
     if (with_readback) TRY(prepare_readback(c, 0, rb_to));
     TRY(capture_graph(c, "hipStreamEndCapture: ", [&]() -> ndt_status {
-        TRY(enqueue_chain(c, slots, mt_possible, false));
+        TRY(enqueue_chain(c, slots, mt_possible));
         if (with_readback) launch_readback(c, 0, rb_to, lead_state(c, slots), 0ull);
         return NDT_OK;
     }, &slot.exec));
     std::memcpy(slot.key, key, sizeof(key));
-    *out = slot.exec;
+    *out = slot.exec.get();
     return NDT_OK;
 }
 
@@ -380,7 +360,7 @@ ndt_status build_graph(ndt_ctx* c, int slots, bool mt_possible, hipGraphExec_t* 
 ndt_status launch_chain(ndt_ctx* c, int slots, bool mt, bool with_readback = false) {
     hipGraphExec_t gx = nullptr;
     TRY(build_graph(c, slots, mt, &gx, with_readback));
-    HIPCHK(c, hipGraphLaunch(gx, c->stream));
+    HIPCHK(c, hipGraphLaunch(gx, c->stream.get()));
     return NDT_OK;
 }
 
@@ -397,12 +377,13 @@ ndt_status enqueue_readback(ndt_ctx* c, int from, int to, const AlignState* d_sr
 ndt_status collect_pass_times(ndt_ctx* c, int hist_before) {
     const int total = std::min(c->h_state->hist_count, c->hist_cap);
     const int ran = total - hist_before;
-    if (ran <= 0 || !c->h_ts) return NDT_OK;
-    const PassRecordDev* hist = c->h_hist + hist_before;
+    if (ran <= 0 || !c->prof.h_ts) return NDT_OK;
+    const PassRecordDev* hist = c->prof.h_hist.get() + hist_before;
+    PassProf::Stats& ps = c->prof.stats;
     double sum = 0, bytes = 0;
     int cnt = 0;
     for (int k = 0; k < ran; ++k) {
-        const unsigned long long* t = &c->h_ts[kTsStride * (size_t)(hist_before + k)];
+        const unsigned long long* t = &c->prof.h_ts[kTsStride * (size_t)(hist_before + k)];
         if (t[1] <= t[0] || t[0] == ~0ull) continue;
         sum += (double)(t[1] - t[0]) * 1e-5;  // 100 MHz ticks -> ms
         bytes += 16.0 * c->N + 36.0 * (double)hist[k].pairs;  // B_pass = 16 N + 36 P
@@ -410,8 +391,8 @@ ndt_status collect_pass_times(ndt_ctx* c, int hist_before) {
         // phases: blocks' bodies, hand-off, partials reduce, control step, state write-back / drain
         if (t[2] >= t[0] && t[3] >= t[2] && t[4] >= t[3] && t[6] >= t[4] && t[7] >= t[6] && t[5] >= t[7] && t[1] >= t[5]) {
             const unsigned long long e[8] = {t[0], t[2], t[3], t[4], t[6], t[7], t[5], t[1]};
-            for (int q = 0; q < 7; ++q) c->prof_phase_sum[q] += (double)(e[q + 1] - e[q]) * 1e-5;
-            ++c->prof_phase_count;
+            for (int q = 0; q < 7; ++q) ps.phase_sum[q] += (double)(e[q + 1] - e[q]) * 1e-5;
+            ++ps.phase_count;
         }
     }
     // profiling build: mean per-workgroup phases of this align's passes (private per-block stamps)
@@ -423,7 +404,7 @@ ndt_status collect_pass_times(ndt_ctx* c, int hist_before) {
         const int nbk = std::min(direct_geom(c, c->lead != 0).nb, kBM);
         for (int k = 0; k < ran && hist_before + k < kBP; ++k) {
             const int pidx = hist_before + k;
-            const unsigned long long t0 = c->h_ts[kTsStride * (size_t)pidx];
+            const unsigned long long t0 = c->prof.h_ts[kTsStride * (size_t)pidx];
             double ph[5] = {0, 0, 0, 0, 0};
             bool ok = true;
             int nb_used = 0;
@@ -454,8 +435,8 @@ ndt_status collect_pass_times(ndt_ctx* c, int hist_before) {
                     fclose(f);
                 }
             }
-            for (int q = 0; q < 5; ++q) c->prof_body_sum[q] += ph[q] / nb_used * 1e-5;
-            ++c->prof_body_count;
+            for (int q = 0; q < 5; ++q) ps.body_sum[q] += ph[q] / nb_used * 1e-5;
+            ++ps.body_count;
             if (c->lead) {
                 // leading-tail kernels: workgroup 0's prologue (staging, partial reduction, control step + tables) in the
                 // tail slots record / machine / solve_setup
@@ -465,38 +446,37 @@ ndt_status collect_pass_times(ndt_ctx* c, int hist_before) {
                 const unsigned long long* tl = pidx >= 1 ? &blk[((size_t)(pidx - 1) * kBM + kBM - 1) * kBS] : nullptr;
                 if (r[1] >= r[0] && r[2] >= r[1] && r[3] >= r[2] && r[0] > 0 && tl && tl[4] >= r[2] && tl[5] >= tl[4] &&
                     tl[1] >= tl[5] && tl[2] >= tl[1] && tl[3] >= tl[2] && r[3] >= tl[3]) {
-                    c->prof_tail_sum[0] += (double)(r[1] - r[0]) * 1e-5;    // record    <- staging
-                    c->prof_tail_sum[1] += (double)(r[2] - r[1]) * 1e-5;    // machine   <- partial reduction
-                    c->prof_tail_sum[2] += (double)(tl[4] - r[2]) * 1e-5;   // solve_setup <- pass record
-                    c->prof_tail_sum[3] += (double)(tl[5] - tl[4]) * 1e-5;  // solve     <- state machine
-                    c->prof_tail_sum[4] += (double)(tl[1] - tl[5]) * 1e-5;  // post_solve <- to the step
-                    c->prof_tail_sum[5] += (double)(tl[2] - tl[1]) * 1e-5;  // sincos    <- step + sin/cos + barrier
-                    c->prof_tail_sum[6] += (double)(tl[3] - tl[2]) * 1e-5;  // rows      <- T + tables
-                    c->prof_tail_sum[7] += (double)(r[3] - tl[3]) * 1e-5;   // writeback <- to the body
-                    ++c->prof_tail_count;
+                    ps.tail_sum[0] += (double)(r[1] - r[0]) * 1e-5;    // record    <- staging
+                    ps.tail_sum[1] += (double)(r[2] - r[1]) * 1e-5;    // machine   <- partial reduction
+                    ps.tail_sum[2] += (double)(tl[4] - r[2]) * 1e-5;   // solve_setup <- pass record
+                    ps.tail_sum[3] += (double)(tl[5] - tl[4]) * 1e-5;  // solve     <- state machine
+                    ps.tail_sum[4] += (double)(tl[1] - tl[5]) * 1e-5;  // post_solve <- to the step
+                    ps.tail_sum[5] += (double)(tl[2] - tl[1]) * 1e-5;  // sincos    <- step + sin/cos + barrier
+                    ps.tail_sum[6] += (double)(tl[3] - tl[2]) * 1e-5;  // rows      <- T + tables
+                    ps.tail_sum[7] += (double)(r[3] - tl[3]) * 1e-5;   // writeback <- to the body
+                    ++ps.tail_count;
                 }
                 continue;
             }
             // tail: [0] before / [1] after the Newton LU solve, [2] sin/cos ready, [3] tables written
             const unsigned long long* tl = &blk[((size_t)pidx * kBM + kBM - 1) * kBS];
-            const unsigned long long* t = &c->h_ts[kTsStride * (size_t)pidx];
+            const unsigned long long* t = &c->prof.h_ts[kTsStride * (size_t)pidx];
             if (tl[4] >= t[6] && tl[5] >= tl[4] && tl[0] >= tl[5] && tl[1] >= tl[0] && t[7] >= tl[1] && tl[2] >= t[7] &&
                 tl[3] >= tl[2] && t[5] >= tl[3]) {
                 const unsigned long long e[9] = {t[6], tl[4], tl[5], tl[0], tl[1], t[7], tl[2], tl[3], t[5]};
-                for (int q = 0; q < 8; ++q) c->prof_tail_sum[q] += (double)(e[q + 1] - e[q]) * 1e-5;
+                for (int q = 0; q < 8; ++q) ps.tail_sum[q] += (double)(e[q + 1] - e[q]) * 1e-5;
                 // the speculative Newton solve on wave 0: its start after staging, its duration
                 if (tl[6] >= t[6] && tl[7] >= tl[6]) {
-                    c->prof_tail_sum[8] += (double)(tl[6] - t[6]) * 1e-5;
-                    c->prof_tail_sum[9] += (double)(tl[7] - tl[6]) * 1e-5;
+                    ps.tail_sum[8] += (double)(tl[6] - t[6]) * 1e-5;
+                    ps.tail_sum[9] += (double)(tl[7] - tl[6]) * 1e-5;
                 }
-                ++c->prof_tail_count;
+                ++ps.tail_count;
             }
         }
     }
-    c->prof_ms_sum += sum;
-    c->prof_bytes_sum += bytes;
-    c->prof_count += cnt;
-    if (c->prof_count) { c->ms_pass_avg = c->prof_ms_sum / c->prof_count; c->pass_bytes_avg = c->prof_bytes_sum / c->prof_count; }
+    ps.ms_sum += sum;
+    ps.bytes_sum += bytes;
+    ps.count += cnt;
     return NDT_OK;
 }
 
@@ -511,7 +491,7 @@ constexpr int kLeadMaxPoints = 262144;  // leading-tail chains below this many s
 ndt_status enqueue_source_order(ndt_ctx* c, const float T[16]) {
     c->pass_src = c->source.p;
     const int n = c->N;
-    if (!c->order_source || n < kOrderMinPoints) return NDT_OK;
+    if (!c->opt.order_source || n < kOrderMinPoints) return NDT_OK;
     TRY(ensure(c, c->source_ord, geom_points(n)));
     TRY(ensure(c, c->ord_k0, n)); TRY(ensure(c, c->ord_v0, n)); TRY(ensure(c, c->ord_k1, n)); TRY(ensure(c, c->ord_v1, n));
     const int items = radix_items(c, n);
@@ -520,16 +500,16 @@ ndt_status enqueue_source_order(ndt_ctx* c, const float T[16]) {
     TRY(ensure(c, c->s.radix_status, radix_status_words(nb_sort)));
     Mat4f Tm;
     std::memcpy(Tm.m, T, sizeof(Tm.m));
-    HIPCHK(c, hipMemsetAsync(c->s.radix_aux.p, 0, kRadixAuxWords * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->s.radix_aux.p, 0, kRadixAuxWords * sizeof(int), c->stream.get()));
     const int nb_keys = std::max(1, std::min(ceil_div(n, kBlock), 1024));
-    hipLaunchKernelGGL(k_src_keys, dim3(nb_keys), dim3(kBlock), 0, c->stream, c->source.p, n, Tm, c->d_hdr, c->ord_k0.p, c->ord_v0.p,
+    hipLaunchKernelGGL(k_src_keys, dim3(nb_keys), dim3(kBlock), 0, c->stream.get(), c->source.p, n, Tm, c->d_hdr.p, c->ord_k0.p, c->ord_v0.p,
                        c->s.radix_aux.p, c->s.radix_status.p, (int)radix_status_words(nb_sort));
     const int passes = radix_launch_passes(c);
     for (int pass = 0; pass < passes; ++pass)
-        launch_radix_pass(c, main_lane(c), items, nb_sort, c->ord_k0.p, c->ord_v0.p, c->ord_k1.p, c->ord_v1.p, n, pass, c->d_hdr, c->d_hdr,
+        launch_radix_pass(c, main_lane(c), items, nb_sort, c->ord_k0.p, c->ord_v0.p, c->ord_k1.p, c->ord_v1.p, n, pass, c->d_hdr.p, c->d_hdr.p,
                           passes - 1);
-    hipLaunchKernelGGL(k_src_gather, dim3(std::max(1, std::min(ceil_div(n, kBlock), 2048))), dim3(kBlock), 0, c->stream, c->source.p,
-                       c->ord_v0.p, c->ord_v1.p, c->d_hdr, c->source_ord.p, n);
+    hipLaunchKernelGGL(k_src_gather, dim3(std::max(1, std::min(ceil_div(n, kBlock), 2048))), dim3(kBlock), 0, c->stream.get(), c->source.p,
+                       c->ord_v0.p, c->ord_v1.p, c->d_hdr.p, c->source_ord.p, n);
     HIPCHK(c, hipGetLastError());
     c->pass_src = c->source_ord.p;
     return NDT_OK;
@@ -539,11 +519,11 @@ ndt_status enqueue_source_order(ndt_ctx* c, const float T[16]) {
 // synchronisation sleeps on the completion interrupt and wakes tens of microseconds after the GPU is done); a device
 // error still surfaces through the periodic stream query.  NDT_SPIN_WAIT=0 synchronises the stream instead (A/B).
 ndt_status wait_readback(ndt_ctx* c, unsigned long long seq) {
-    const volatile unsigned long long* w = c->h_rb;
+    const volatile unsigned long long* w = c->h_rb.get();
     for (unsigned it = 1;; ++it) {
         if (*w == seq) break;
         if ((it & 1023u) == 0) {
-            const hipError_t e = hipStreamQuery(c->stream);
+            const hipError_t e = hipStreamQuery(c->stream.get());
             if (e == hipSuccess) {
                 if (*w == seq) break;
                 return fail(c, NDT_EDEVICE, "align read-back missing after the stream finished");
@@ -564,7 +544,7 @@ ndt_status wait_readback(ndt_ctx* c, unsigned long long seq) {
 ndt_status align_enqueue(ndt_ctx* c, const float guess[16]) {
     TRY(ensure_align_buffers(c));
     std::memcpy(c->al_guess, guess, sizeof(c->al_guess));
-    init_state(c, guess, c->h_state);
+    init_state(c, guess, c->h_state.get());
     const bool mt = c->h_state->mt_possible != 0;
     // Newton-only chains: the first round covers the previous align's pass count + 1 (scan-to-scan replay converges
     // in a similar number of iterations), continuation rounds 8 passes; passes queued after convergence exit at
@@ -574,17 +554,17 @@ ndt_status align_enqueue(ndt_ctx* c, const float guess[16]) {
     // streams' bodies fill the CUs a last-workgroup tail leaves idle: C4 1437 vs 1156 pairs/s) and below kLeadMaxPoints
     // source points (C5's 1 M-point passes are body-bound: 227.7 vs 225.3 scans/s); C2 954 -> 1022, C3 2219 -> 2334.
     // ndt_set_pass_options(lead_tail = 0) forces last-workgroup tails (tests/test_gpu_lead.py compares the two chains)
-    c->lead = (c->opt_lead_tail && !c->no_lead && c->N < kLeadMaxPoints && needs_direct(c->prm) && !needs_radius(c->prm, mt)) ? 1 : 0;
+    c->lead = (c->opt.lead_tail && !c->no_lead && c->N < kLeadMaxPoints && needs_direct(c->prm) && !needs_radius(c->prm, mt)) ? 1 : 0;
     c->lead_par = 0;
     // a leading-tail chain needs one kernel more than it has passes (the last pass's step runs in the next kernel)
     const int full = mt ? 16 : c->prm.max_iter + 3 + c->lead;
     int slots = full;
     if (!mt && c->last_passes > 0) slots = std::min(full, std::max(3, c->last_passes + 1 + c->lead));
-    if (c->profiling) TRY(ensure(c, c->ts, kTsStride * (size_t)c->hist_cap));
+    if (c->opt.profiling) TRY(ensure(c, c->prof.ts, kTsStride * (size_t)c->hist_cap));
     {
         // state upload + ticket reset (+ stamp reset) + the align's start stamp as one launch; the state is passed by
         // value (kernel argument)
-        const int ts_words = c->profiling ? kTsStride * c->hist_cap : 0;
+        const int ts_words = c->opt.profiling ? kTsStride * c->hist_cap : 0;
         // + the source copy ndt_set_source_device deferred (four 16-byte words per thread and round; a source that is not
         // 16-byte aligned is copied by copy16 first)
         if (c->src_pend && (reinterpret_cast<uintptr_t>(c->src_pend) & 15)) TRY(flush_source(c));
@@ -593,9 +573,9 @@ ndt_status align_enqueue(ndt_ctx* c, const float guess[16]) {
         const uint4* cp_src = reinterpret_cast<const uint4*>(c->src_pend);
         c->src_pend = nullptr;
         c->al_seq = ++c->rb_seq;
-        c->lanes_marked = 0;  // a side-lane mark not taken before this align is dropped
-        hipLaunchKernelGGL(k_align_init, dim3(nb), dim3(kBlock), 0, c->stream, *c->h_state, c->d_state, c->counter.p,
-                           c->profiling ? c->ts.p : nullptr, ts_words, c->d_clk, c->grid_valid ? c->d_hdr : nullptr, c->al_seq,
+        c->lanes.marked = 0;  // a side-lane mark not taken before this align is dropped
+        hipLaunchKernelGGL(k_align_init, dim3(nb), dim3(kBlock), 0, c->stream.get(), *c->h_state, c->d_state.p, c->counter.p,
+                           c->opt.profiling ? c->prof.ts.p : nullptr, ts_words, c->d_clk.p, c->grid_valid ? c->d_hdr.p : nullptr, c->al_seq,
                            cp_src, reinterpret_cast<uint4*>(c->source.p), cp_words);
         HIPCHK(c, hipGetLastError());
     }
@@ -621,11 +601,11 @@ ndt_status align_finish_once(ndt_ctx* c) {
     for (;;) {
         TRY(wait_readback(c, c->al_seq));
         ++rounds;
-        if (c->profiling) TRY(collect_pass_times(c, hist_before));
+        if (c->opt.profiling) TRY(collect_pass_times(c, hist_before));
         if (c->h_state->done || rounds >= max_rounds) break;
         if (!mt) slots = std::min(full, 8);
         if (c->h_state->needs_svd) {
-            hipLaunchKernelGGL(k_svd_resume, dim3(1), dim3(kBlock), 0, c->stream, lead_state(c, 0));
+            hipLaunchKernelGGL(k_svd_resume, dim3(1), dim3(kBlock), 0, c->stream.get(), lead_state(c, 0));
             HIPCHK(c, hipGetLastError());
         }
         hist_before = std::min(c->h_state->hist_count, c->hist_cap);
@@ -639,7 +619,7 @@ ndt_status align_finish_once(ndt_ctx* c) {
     c->built_since_align = false;
     c->grid_cells_seen = std::max(c->grid_cells_seen, c->h_state->grid_cells);
     c->have_result = true;
-    c->last_icp = false;
+    c->icp.last = false;
     c->align_tgt_gen = c->tgt_gen;
     c->last_passes = c->h_state->n_passes;
     if (!c->h_state->done) return fail(c, NDT_EDEVICE, "align did not finish within the slot budget");
@@ -673,7 +653,7 @@ ndt_status run_align(ndt_ctx* c, const float guess[16]) {
 }
 
 void fill_result(ndt_ctx* c, ndt_result* out) {
-    const AlignState* st = c->h_state;
+    const AlignState* st = c->h_state.get();
     for (int k = 0; k < 16; ++k) out->final_tf[k] = st->T[k];
     out->nr_iterations = st->nr_iterations;
     out->converged = st->converged;
@@ -693,23 +673,23 @@ static ndt_status single_pass(ndt_ctx* c, const double p[6], const float T[16], 
     TRY(ensure_align_buffers(c));
     TRY(ensure(c, c->reduce_out, kNumAcc));
     c->pass_src = c->source.p;
-    AlignState* st = c->h_state;
+    AlignState* st = c->h_state.get();
     init_state(c, T, st);
     for (int k = 0; k < 16; ++k) st->T[k] = T[k];
     for (int k = 0; k < 6; ++k) { st->p[k] = p[k]; st->x_eval[k] = p[k]; st->x_t[k] = p[k]; }
     angle_tables(p, st->jang, st->hang, st->jang_d, st->hang_d);
     st->pass_kind = kind;
     st->pending = 1;
-    HIPCHK(c, hipMemcpyAsync(c->d_state, st, sizeof(AlignState), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->counter.p, 0, kPassCounterWords * sizeof(unsigned), c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_state.p, st, sizeof(AlignState), hipMemcpyHostToDevice, c->stream.get()));
+    HIPCHK(c, hipMemsetAsync(c->counter.p, 0, kPassCounterWords * sizeof(unsigned), c->stream.get()));
     if (kind == PASS_HESS || force_radius || !needs_direct(c->prm)) launch_radius(c, 1);
     else launch_pass(c, 1);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(res44, c->reduce_out.p, kNumAcc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(res44, c->reduce_out.p, kNumAcc * sizeof(double), hipMemcpyDeviceToHost, c->stream.get()));
     // the target's cell count sizes the next dense grid, as an align's read-back does (align_finish)
     long long cells = 0;
-    HIPCHK(c, hipMemcpyAsync(&cells, &c->d_hdr->cells, sizeof(cells), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(&cells, &c->d_hdr.p->cells, sizeof(cells), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     c->grid_cells_seen = std::max(c->grid_cells_seen, cells);
     c->have_result = false;
     return NDT_OK;
@@ -773,19 +753,19 @@ ndt_status ndt_get_output(ndt_ctx* c, float* xyz, size_t stride_bytes) {
     TRY(set_dev(c));
     TRY(flush_source(c));
     TRY(ensure(c, c->out_cloud, c->N));
-    if (c->last_icp) {
+    if (c->icp.last) {
         // an ICP align: the source transformed by its final transformation (PCL returns the cloud it transformed
         // cumulatively, iteration by iteration: the same points up to f32 rounding)
         Mat4f Tm;
-        for (int k = 0; k < 16; ++k) Tm.m[k] = c->icp_final[k];
-        hipLaunchKernelGGL(k_transform_mat, dim3(std::max(1, ceil_div(c->N, kBlock))), dim3(kBlock), 0, c->stream, c->source.p, c->N, Tm,
+        for (int k = 0; k < 16; ++k) Tm.m[k] = c->icp.final_tf[k];
+        hipLaunchKernelGGL(k_transform_mat, dim3(std::max(1, ceil_div(c->N, kBlock))), dim3(kBlock), 0, c->stream.get(), c->source.p, c->N, Tm,
                            c->out_cloud.p);
     } else
-    hipLaunchKernelGGL(k_transform, dim3(std::max(1, ceil_div(c->N, kBlock))), dim3(kBlock), 0, c->stream, c->source.p, c->N, c->d_state,
+    hipLaunchKernelGGL(k_transform, dim3(std::max(1, ceil_div(c->N, kBlock))), dim3(kBlock), 0, c->stream.get(), c->source.p, c->N, c->d_state.p,
                        c->out_cloud.p);
     std::vector<float4> tmp(c->N);
-    if (c->N) HIPCHK(c, hipMemcpyAsync(tmp.data(), c->out_cloud.p, c->N * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->N) HIPCHK(c, hipMemcpyAsync(tmp.data(), c->out_cloud.p, c->N * sizeof(float4), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     char* base = reinterpret_cast<char*>(xyz);
     for (int i = 0; i < c->N; ++i) {
         float* f = reinterpret_cast<float*>(base + (size_t)i * stride_bytes);
@@ -799,7 +779,7 @@ ndt_status ndt_get_history(ndt_ctx* c, ndt_pass_record* out, int cap, int* n_out
     TRY(set_dev(c));
     const int n = std::min(std::min(c->h_state->hist_count, c->hist_cap), std::max(cap, 0));
     std::vector<PassRecordDev> tmp(n);
-    if (n) HIPCHK(c, hipMemcpy(tmp.data(), c->d_hist, n * sizeof(PassRecordDev), hipMemcpyDeviceToHost));
+    if (n) HIPCHK(c, hipMemcpy(tmp.data(), c->d_hist.p, n * sizeof(PassRecordDev), hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) {
         out[i].kind = tmp[i].kind;
         out[i].newton_iter = tmp[i].newton_iter;
@@ -845,12 +825,12 @@ ndt_status ndt_calculate_score(ndt_ctx* c, const float T[16], double* out) {
     Mat4f Tm;
     for (int k = 0; k < 16; ++k) Tm.m[k] = T[k];
     const double d1 = c->gauss_cur[0], d2 = c->gauss_cur[1], d3 = c->gauss_cur[2];
-    hipLaunchKernelGGL(k_score_radius, dim3(nb), dim3(kBlock), 0, c->stream, c->source.p, c->N, Tm, c->d_hdr, c->table.p, c->grid.p,
+    hipLaunchKernelGGL(k_score_radius, dim3(nb), dim3(kBlock), 0, c->stream.get(), c->source.p, c->N, Tm, c->d_hdr.p, c->table.p, c->grid.p,
                        c->recs.p, c->cent.p, c->icovd.p, d1, d2, d3, c->prm.resolution, c->score_part.p);
     HIPCHK(c, hipGetLastError());
     std::vector<double> part(nb);
-    HIPCHK(c, hipMemcpyAsync(part.data(), c->score_part.p, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(part.data(), c->score_part.p, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     double score = 0.0;
     for (int b = 0; b < nb; ++b) score += part[b];
     *out = score / (double)c->N;
@@ -897,20 +877,12 @@ ndt_status ndt_align_batch(ndt_ctx* c, const ndt_pair_desc* pairs, int n_pairs, 
     for (int k = 0; k < streams - 1; ++k) {
         ndt_ctx* h = c->helpers[k];
         h->prm = c->prm;
-        h->profiling = c->profiling;
-        // the ctx's pass / build options (a helper created after ndt_set_pass_options / ndt_set_build_options gets them too)
-        h->opt_lead_tail = c->opt_lead_tail;
-        h->opt_ppt = c->opt_ppt;
-        h->order_source = c->order_source;
-        h->radix_force = c->radix_force;
-        h->tile_tickets = h->tile_tickets || c->tile_tickets;
+        hand_options(h, c);  // a helper created after ndt_set_pass_options / ndt_set_build_options gets them too
         ctxs.push_back(h);
     }
     // every registration in flight spreads its passes over all CUs (spreading each over n_cu / streams CUs was
     // measured neutral) and keeps last-workgroup tails (the other streams' bodies fill the CUs a tail leaves idle)
-    // (A/B: NDT_BATCH_LEAD=1 lets them run leading-tail chains)
-    static const bool batch_lead = std::getenv("NDT_BATCH_LEAD") != nullptr;
-    for (ndt_ctx* x : ctxs) x->no_lead = streams > 1 && !batch_lead;
+    for (ndt_ctx* x : ctxs) x->no_lead = streams > 1;
     std::vector<int> slot_pair(streams, -1);
     ndt_status rs = NDT_OK;
     auto drain = [&](int k) -> ndt_status {

@@ -4,14 +4,14 @@
 
 // pcl::VoxelGrid over n device points: the voxel means in out (room for n points), their count in *n_out
 static ndt_status voxel_downsample_dev(ndt_ctx* c, const float4* in, size_t n, float leaf, float4* out, size_t* n_out) {
-    TRY(enqueue_bin_and_sort(c, main_lane(c), in, (int)n, 1, c->d_hdr_ds, leaf));
-    TRY(enqueue_downsample_finalize(c, main_lane(c), c->d_hdr_ds, in, (int)n, out));
-    HIPCHK(c, hipMemcpyAsync(c->h_hdr, c->d_hdr_ds, sizeof(GridHeader), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    TRY(enqueue_bin_and_sort(c, main_lane(c), in, (int)n, 1, c->d_hdr_ds.p, leaf));
+    TRY(enqueue_downsample_finalize(c, main_lane(c), c->d_hdr_ds.p, in, (int)n, out));
+    HIPCHK(c, hipMemcpyAsync(c->h_hdr.get(), c->d_hdr_ds.p, sizeof(GridHeader), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     if (c->h_hdr->pad[0]) return fail(c, NDT_EDEVICE, "voxel downsample: radix look-back timed out");
     if (c->h_hdr->overflow) {
         // pcl::VoxelGrid: "Leaf size is too small for the input dataset" -> output = input copy
-        HIPCHK(c, hipMemcpyAsync(out, in, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out, in, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream.get()));
         *n_out = n;
         c->err = "voxel downsample: leaf size too small, output = input";
         return NDT_EOVERFLOW;
@@ -28,7 +28,7 @@ ndt_status ndt_transform_device(ndt_ctx* c, const float T[16], const float* d_in
     if (n == 0) return NDT_OK;
     Mat4f Tm;
     for (int k = 0; k < 16; ++k) Tm.m[k] = T[k];
-    hipLaunchKernelGGL(k_transform_mat, dim3(ceil_div((long long)n, kBlock)), dim3(kBlock), 0, c->stream,
+    hipLaunchKernelGGL(k_transform_mat, dim3(ceil_div((long long)n, kBlock)), dim3(kBlock), 0, c->stream.get(),
                        reinterpret_cast<const float4*>(d_in4), (int)n, Tm, reinterpret_cast<float4*>(d_out4));
     HIPCHK(c, hipGetLastError());
     return NDT_OK;
@@ -50,14 +50,14 @@ ndt_status ndt_voxel_downsample(ndt_ctx* c, const float* xyzi, size_t n, size_t 
         tmp[i] = make_float4(f[0], f[1], f[2], f[intensity_offset]);
     }
     TRY(ensure(c, in, n)); TRY(ensure(c, outb, n));
-    HIPCHK(c, hipMemcpyAsync(in.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(in.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream.get()));
     const ndt_status rs = voxel_downsample_dev(c, in.p, n, leaf, outb.p, n_out);
     if (rs != NDT_OK && rs != NDT_EOVERFLOW) return rs;
     // the voxel means, or after an overflow the input copy
     const size_t m = std::min(cap, *n_out);
     std::vector<float4> o(m);
-    if (m) HIPCHK(c, hipMemcpyAsync(o.data(), outb.p, m * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (m) HIPCHK(c, hipMemcpyAsync(o.data(), outb.p, m * sizeof(float4), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     for (size_t i = 0; i < m; ++i) { out4[4 * i] = o[i].x; out4[4 * i + 1] = o[i].y; out4[4 * i + 2] = o[i].z; out4[4 * i + 3] = o[i].w; }
     return rs;
 }
@@ -92,82 +92,82 @@ ndt_status ndt_filter_scan_device(ndt_ctx* c, const ndt_filter_params* prm, cons
         return fail(c, NDT_EINVAL, "bad filter args");
     TRY(set_dev(c));
     *n_out = 0;
-    c->fe_nvox = 0;
+    c->fe.nvox = 0;
     if (n == 0) return NDT_OK;
     const int N = (int)n;
     const float4* in = reinterpret_cast<const float4*>(d_in4);
     float4* out = reinterpret_cast<float4*>(d_out4);
-    TRY(ensure(c, c->fe_flags, n)); TRY(ensure(c, c->fe_idx, n)); TRY(ensure(c, c->fe_crop, n));
-    TRY(ensure(c, c->fe_ds, n)); TRY(ensure(c, c->fe_dist, n)); TRY(ensure(c, c->fe_thr, 4));
+    TRY(ensure(c, c->fe.flags, n)); TRY(ensure(c, c->fe.idx, n)); TRY(ensure(c, c->fe.crop, n));
+    TRY(ensure(c, c->fe.ds, n)); TRY(ensure(c, c->fe.dist, n)); TRY(ensure(c, c->fe.thr, 4));
     const int nb = std::max(1, std::min(ceil_div(N, kBlock), 2048));
     // the compaction scans write their count to d_hdr_fe->pad[1] and raise a look-back timeout in d_hdr_fe->pad[0] (its own
     // header: the VoxelGrid build rewrites d_hdr_ds); both come back in one copy into pinned memory.  The flag is cleared
     // only after it was raised.
     int* fw = c->h_async->fe_words;
     auto scan_failed = [&](const char* what) -> ndt_status {
-        (void)hipMemsetAsync(&c->d_hdr_fe->pad[0], 0, sizeof(int), c->stream);
+        (void)hipMemsetAsync(&c->fe.d_hdr.p->pad[0], 0, sizeof(int), c->stream.get());
         return fail(c, NDT_EDEVICE, std::string("filter: ") + what + " compaction scan: look-back timed out");
     };
     // 1. removeNaNFromPointCloud + range crop (filter_node.cpp:236-247), input order kept
-    hipLaunchKernelGGL(k_crop_flags, dim3(nb), dim3(kBlock), 0, c->stream, in, N, prm->r_min, prm->r_max, c->fe_flags.p);
-    TRY(enqueue_scan(c, main_lane(c), c->fe_flags.p, N, nullptr, c->fe_idx.p, &c->d_hdr_fe->pad[1], c->d_hdr_fe));
-    hipLaunchKernelGGL(k_compact4, dim3(nb), dim3(kBlock), 0, c->stream, in, c->fe_flags.p, c->fe_idx.p, N, c->fe_crop.p);
-    HIPCHK(c, hipMemcpyAsync(fw, &c->d_hdr_fe->pad[0], 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipLaunchKernelGGL(k_crop_flags, dim3(nb), dim3(kBlock), 0, c->stream.get(), in, N, prm->r_min, prm->r_max, c->fe.flags.p);
+    TRY(enqueue_scan(c, main_lane(c), c->fe.flags.p, N, nullptr, c->fe.idx.p, &c->fe.d_hdr.p->pad[1], c->fe.d_hdr.p));
+    hipLaunchKernelGGL(k_compact4, dim3(nb), dim3(kBlock), 0, c->stream.get(), in, c->fe.flags.p, c->fe.idx.p, N, c->fe.crop.p);
+    HIPCHK(c, hipMemcpyAsync(fw, &c->fe.d_hdr.p->pad[0], 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     if (fw[0]) return scan_failed("crop");
     const int m = fw[1];
     if (m == 0) return NDT_OK;
     // 2. VoxelGrid (filter_node.cpp:249-251)
-    TRY(enqueue_bin_and_sort(c, main_lane(c), c->fe_crop.p, m, 1, c->d_hdr_ds, prm->leaf));
-    TRY(enqueue_downsample_finalize(c, main_lane(c), c->d_hdr_ds, c->fe_crop.p, m, c->fe_ds.p));
-    HIPCHK(c, hipMemcpyAsync(c->h_hdr, c->d_hdr_ds, sizeof(GridHeader), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    TRY(enqueue_bin_and_sort(c, main_lane(c), c->fe.crop.p, m, 1, c->d_hdr_ds.p, prm->leaf));
+    TRY(enqueue_downsample_finalize(c, main_lane(c), c->d_hdr_ds.p, c->fe.crop.p, m, c->fe.ds.p));
+    HIPCHK(c, hipMemcpyAsync(c->h_hdr.get(), c->d_hdr_ds.p, sizeof(GridHeader), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     if (c->h_hdr->pad[0]) return fail(c, NDT_EDEVICE, "filter: VoxelGrid sort: radix look-back timed out");
     int nv = c->h_hdr->n_leaves;
     if (c->h_hdr->overflow) {  // pcl::VoxelGrid: leaf too small -> output = input copy
-        HIPCHK(c, hipMemcpyAsync(c->fe_ds.p, c->fe_crop.p, (size_t)m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->fe.ds.p, c->fe.crop.p, (size_t)m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream.get()));
         nv = m;
     }
-    c->fe_nvox = (size_t)nv;
+    c->fe.nvox = (size_t)nv;
     const int nbq = std::max(1, std::min(ceil_div(nv, kBlock / 16), 16384));  // 16-lane team per query
     if (prm->outlier_method == 1) {
         // 3'. RadiusOutlierRemoval (filter_node.cpp:265-272): index cell just above the radius (one ring of cells)
-        TRY(enqueue_nn_index(c, main_lane(c), c->fe_ds.p, nv, 1, (float)(1.01 * prm->ror_radius), c->sor_ix));
-        hipLaunchKernelGGL(k_ror_keep, dim3(nbq), dim3(kBlock), 0, c->stream, c->fe_ds.p, nv, prm->ror_radius, prm->ror_min_neighbors,
-                           c->sor_ix.hdr, c->sor_ix.blk.p, c->sor_ix.off.p, c->sor_ix.pts.p, c->fe_flags.p);
+        TRY(enqueue_nn_index(c, main_lane(c), c->fe.ds.p, nv, 1, (float)(1.01 * prm->ror_radius), c->fe.sor_ix));
+        hipLaunchKernelGGL(k_ror_keep, dim3(nbq), dim3(kBlock), 0, c->stream.get(), c->fe.ds.p, nv, prm->ror_radius, prm->ror_min_neighbors,
+                           c->fe.sor_ix.hdr.p, c->fe.sor_ix.blk.p, c->fe.sor_ix.off.p, c->fe.sor_ix.pts.p, c->fe.flags.p);
     } else {
         // 3. StatisticalOutlierRemoval (filter_node.cpp:253-263)
         if (nv <= prm->mean_k) {
-            HIPCHK(c, hipMemcpyAsync(out, c->fe_ds.p, (size_t)nv * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipMemcpyAsync(out, c->fe.ds.p, (size_t)nv * sizeof(float4), hipMemcpyDeviceToDevice, c->stream.get()));
+            HIPCHK(c, hipStreamSynchronize(c->stream.get()));
             *n_out = (size_t)nv;
             return NDT_OK;
         }
         // k-NN index over the voxel-filtered cloud: base cell 3 leaves (the mean_k = 30 neighbours of a surface point lie
         // within the 3x3x3 cells around it on a 0.5 m grid)
-        TRY(enqueue_nn_index(c, main_lane(c), c->fe_ds.p, nv, 1, 3.0f * prm->leaf, c->sor_ix));
+        TRY(enqueue_nn_index(c, main_lane(c), c->fe.ds.p, nv, 1, 3.0f * prm->leaf, c->fe.sor_ix));
         if (prm->mean_k + 1 <= 32)
-            hipLaunchKernelGGL(k_sor_knn<32>, dim3(nbq), dim3(kBlock), 0, c->stream, c->fe_ds.p, nv, prm->mean_k, c->sor_ix.hdr,
-                               c->sor_ix.blk.p, c->sor_ix.off.p, c->sor_ix.pts.p, c->fe_dist.p);
+            hipLaunchKernelGGL(k_sor_knn<32>, dim3(nbq), dim3(kBlock), 0, c->stream.get(), c->fe.ds.p, nv, prm->mean_k, c->fe.sor_ix.hdr.p,
+                               c->fe.sor_ix.blk.p, c->fe.sor_ix.off.p, c->fe.sor_ix.pts.p, c->fe.dist.p);
         else
-            hipLaunchKernelGGL(k_sor_knn<64>, dim3(nbq), dim3(kBlock), 0, c->stream, c->fe_ds.p, nv, prm->mean_k, c->sor_ix.hdr,
-                               c->sor_ix.blk.p, c->sor_ix.off.p, c->sor_ix.pts.p, c->fe_dist.p);
-        hipLaunchKernelGGL(k_sor_stats, dim3(1), dim3(kBlock), 0, c->stream, c->fe_dist.p, nv, prm->stddev_mul, c->fe_thr.p);
+            hipLaunchKernelGGL(k_sor_knn<64>, dim3(nbq), dim3(kBlock), 0, c->stream.get(), c->fe.ds.p, nv, prm->mean_k, c->fe.sor_ix.hdr.p,
+                               c->fe.sor_ix.blk.p, c->fe.sor_ix.off.p, c->fe.sor_ix.pts.p, c->fe.dist.p);
+        hipLaunchKernelGGL(k_sor_stats, dim3(1), dim3(kBlock), 0, c->stream.get(), c->fe.dist.p, nv, prm->stddev_mul, c->fe.thr.p);
         const int nbk = std::max(1, std::min(ceil_div(nv, kBlock), 2048));
-        hipLaunchKernelGGL(k_sor_keep, dim3(nbk), dim3(kBlock), 0, c->stream, c->fe_dist.p, nv, c->fe_thr.p, c->fe_flags.p);
+        hipLaunchKernelGGL(k_sor_keep, dim3(nbk), dim3(kBlock), 0, c->stream.get(), c->fe.dist.p, nv, c->fe.thr.p, c->fe.flags.p);
     }
     const int nbv = std::max(1, std::min(ceil_div(nv, kBlock), 2048));
-    TRY(enqueue_scan(c, main_lane(c), c->fe_flags.p, nv, nullptr, c->fe_idx.p, &c->d_hdr_fe->pad[1], c->d_hdr_fe));
-    hipLaunchKernelGGL(k_compact4, dim3(nbv), dim3(kBlock), 0, c->stream, c->fe_ds.p, c->fe_flags.p, c->fe_idx.p, nv, out);
+    TRY(enqueue_scan(c, main_lane(c), c->fe.flags.p, nv, nullptr, c->fe.idx.p, &c->fe.d_hdr.p->pad[1], c->fe.d_hdr.p));
+    hipLaunchKernelGGL(k_compact4, dim3(nbv), dim3(kBlock), 0, c->stream.get(), c->fe.ds.p, c->fe.flags.p, c->fe.idx.p, nv, out);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(fw, &c->d_hdr_fe->pad[0], 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(fw, &c->fe.d_hdr.p->pad[0], 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream.get()));
     // the outlier filter's neighbour index (enqueue_nn_index: its own sort, header rewritten per build) flags its
     // look-back timeouts in sor_ix.hdr
-    HIPCHK(c, hipMemcpyAsync(&fw[2], &c->sor_ix.hdr->pad[0], sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(&fw[2], &c->fe.sor_ix.hdr.p->pad[0], sizeof(int), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     if (fw[2]) {
         // a compaction-scan flag raised beside it is cleared too, or the next call would report a stale timeout
-        if (fw[0]) (void)hipMemsetAsync(&c->d_hdr_fe->pad[0], 0, sizeof(int), c->stream);
+        if (fw[0]) (void)hipMemsetAsync(&c->fe.d_hdr.p->pad[0], 0, sizeof(int), c->stream.get());
         return fail(c, NDT_EDEVICE, "filter: outlier neighbour index sort: radix look-back timed out");
     }
     if (fw[0]) return scan_failed("outlier");
@@ -189,13 +189,13 @@ ndt_status ndt_filter_scan(ndt_ctx* c, const ndt_filter_params* prm, const float
         const float* f = reinterpret_cast<const float*>(base + i * stride_bytes);
         tmp[i] = make_float4(f[0], f[1], f[2], f[intensity_offset]);
     }
-    TRY(ensure(c, c->fe_in, n)); TRY(ensure(c, c->fe_out, n));
-    HIPCHK(c, hipMemcpyAsync(c->fe_in.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    TRY(ndt_filter_scan_device(c, prm, reinterpret_cast<const float*>(c->fe_in.p), n, reinterpret_cast<float*>(c->fe_out.p), n_out));
+    TRY(ensure(c, c->fe.in, n)); TRY(ensure(c, c->fe.out, n));
+    HIPCHK(c, hipMemcpyAsync(c->fe.in.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream.get()));
+    TRY(ndt_filter_scan_device(c, prm, reinterpret_cast<const float*>(c->fe.in.p), n, reinterpret_cast<float*>(c->fe.out.p), n_out));
     const size_t k = std::min(cap, *n_out);
     if (k) {
         std::vector<float4> o(k);
-        HIPCHK(c, hipMemcpy(o.data(), c->fe_out.p, k * sizeof(float4), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(o.data(), c->fe.out.p, k * sizeof(float4), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < k; ++i) { out4[4 * i] = o[i].x; out4[4 * i + 1] = o[i].y; out4[4 * i + 2] = o[i].z; out4[4 * i + 3] = o[i].w; }
     }
     return NDT_OK;
@@ -204,11 +204,11 @@ ndt_status ndt_filter_scan(ndt_ctx* c, const ndt_filter_params* prm, const float
 ndt_status ndt_filter_last_stats(ndt_ctx* c, float* dist, size_t cap, size_t* n_voxel, double thr[3]) {
     if (!c || !n_voxel) return fail(c, NDT_EINVAL, "null argument");
     TRY(set_dev(c));
-    *n_voxel = c->fe_nvox;
-    const size_t k = std::min(cap, c->fe_nvox);
-    if (dist && k) HIPCHK(c, hipMemcpy(dist, c->fe_dist.p, k * sizeof(float), hipMemcpyDeviceToHost));
+    *n_voxel = c->fe.nvox;
+    const size_t k = std::min(cap, c->fe.nvox);
+    if (dist && k) HIPCHK(c, hipMemcpy(dist, c->fe.dist.p, k * sizeof(float), hipMemcpyDeviceToHost));
     if (thr) {
-        if (c->fe_thr.p) HIPCHK(c, hipMemcpy(thr, c->fe_thr.p, 3 * sizeof(double), hipMemcpyDeviceToHost));
+        if (c->fe.thr.p) HIPCHK(c, hipMemcpy(thr, c->fe.thr.p, 3 * sizeof(double), hipMemcpyDeviceToHost));
         else thr[0] = thr[1] = thr[2] = 0.0;
     }
     return NDT_OK;

@@ -10,31 +10,30 @@
 constexpr int kIcpRun = 8;
 
 static ndt_status icp_graph(ndt_ctx* c, int run, int nb, hipGraphExec_t* out) {
-    const long long key[12] = {run, nb, c->N, (long long)(uintptr_t)c->icp_x.p, (long long)(uintptr_t)c->fit_ix.blk.p,
+    const long long key[12] = {run, nb, c->N, (long long)(uintptr_t)c->icp.x.p, (long long)(uintptr_t)c->fit_ix.blk.p,
                                (long long)(uintptr_t)c->fit_ix.off.p, (long long)(uintptr_t)c->fit_ix.pts.p,
-                               (long long)(uintptr_t)c->fit_ix.idx.p, (long long)(uintptr_t)c->icp_match.p,
-                               (long long)(uintptr_t)c->icp_d2.p, (long long)(uintptr_t)c->icp_part.p,
-                               (long long)(uintptr_t)c->icp_ticket.p};
-    if (c->icp_graph && std::memcmp(key, c->icp_graph_key, sizeof(key)) == 0) {
-        *out = c->icp_graph;
+                               (long long)(uintptr_t)c->fit_ix.idx.p, (long long)(uintptr_t)c->icp.match.p,
+                               (long long)(uintptr_t)c->icp.d2.p, (long long)(uintptr_t)c->icp.part.p,
+                               (long long)(uintptr_t)c->icp.ticket.p};
+    if (c->icp.graph && std::memcmp(key, c->icp.graph_key, sizeof(key)) == 0) {
+        *out = c->icp.graph.get();
         return NDT_OK;
     }
-    if (c->icp_graph) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipGraphExecDestroy(c->icp_graph);
-        c->icp_graph = nullptr;
+    if (c->icp.graph) {
+        HIPCHK(c, hipStreamSynchronize(c->stream.get()));
+        c->icp.graph.reset();
     }
     TRY(capture_graph(c, "ICP graph capture: ", [&]() -> ndt_status {
         for (int k = 0; k < run; ++k)
-            hipLaunchKernelGGL(k_icp_pass, dim3(nb), dim3(kIcpBlock), 0, c->stream, c->icp_x.p, c->N, c->d_icp, c->fit_ix.hdr, c->fit_ix.blk.p,
-                               c->fit_ix.off.p, c->fit_ix.pts.p, c->fit_ix.idx.p, c->icp_match.p, c->icp_d2.p, c->icp_part.p,
-                               c->icp_ticket.p, c->d_icp_hist);
-        const hipError_t e = hipMemcpyAsync(&c->h_icp[0], c->d_icp, sizeof(IcpState), hipMemcpyDeviceToHost, c->stream);
+            hipLaunchKernelGGL(k_icp_pass, dim3(nb), dim3(kIcpBlock), 0, c->stream.get(), c->icp.x.p, c->N, c->icp.d_state.p, c->fit_ix.hdr.p, c->fit_ix.blk.p,
+                               c->fit_ix.off.p, c->fit_ix.pts.p, c->fit_ix.idx.p, c->icp.match.p, c->icp.d2.p, c->icp.part.p,
+                               c->icp.ticket.p, c->icp.d_hist.p);
+        const hipError_t e = hipMemcpyAsync(&c->icp.h_state[0], c->icp.d_state.p, sizeof(IcpState), hipMemcpyDeviceToHost, c->stream.get());
         if (e != hipSuccess) return fail(c, NDT_EDEVICE, std::string("ICP graph capture: ") + hipGetErrorString(e));
         return NDT_OK;
-    }, &c->icp_graph));
-    std::memcpy(c->icp_graph_key, key, sizeof(key));
-    *out = c->icp_graph;
+    }, &c->icp.graph));
+    std::memcpy(c->icp.graph_key, key, sizeof(key));
+    *out = c->icp.graph.get();
     return NDT_OK;
 }
 
@@ -64,37 +63,43 @@ ndt_status ndt_icp_align(ndt_ctx* c, const ndt_icp_params* prm, const float gues
     TRY(set_dev(c));
     TRY(flush_source(c));
     // the target's nearest-neighbour index (getFitnessScore's), with the points' original indices from now on
-    if (!c->icp_used) {
-        c->icp_used = true;
+    if (!c->icp.used) {
+        c->icp.used = true;
         c->fit_valid = false;  // rebuilt behind the fit lane's queued queries (FIFO)
     }
     TRY(ensure_fit_index(c));
     {
         std::string msg;
-        const ndt_status st = c->fit_worker->take_error(&msg);  // the index build has been issued
+        const ndt_status st = c->lanes.fit_worker->take_error(&msg);  // the index build has been issued
         if (st != NDT_OK) {
             c->fit_valid = false;
-            c->fit_pending = false;
+            c->lanes.fit_pending = false;
             return fail(c, st, "ICP: nearest-neighbour index: " + msg);
         }
     }
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_fit_tgt, 0));
-    if (!c->d_icp) {
-        if (hipMalloc(&c->d_icp, sizeof(IcpState)) != hipSuccess || hipMalloc(&c->d_icp_hist, sizeof(IcpRecordDev) * kIcpMaxHistory) != hipSuccess ||
-            hipHostMalloc(&c->h_icp, 2 * sizeof(IcpState), hipHostMallocCoherent) != hipSuccess)
+    HIPCHK(c, hipStreamWaitEvent(c->stream.get(), c->lanes.ev_fit_tgt.get(), 0));
+    if (!c->icp.h_state) {  // the device state, its history and the pinned copies: all three or none
+        DevBuf<IcpState> d_state;
+        DevBuf<IcpRecordDev> d_hist;
+        Pinned<IcpState[]> h_state;
+        if (ensure(c, d_state, 1) != NDT_OK || ensure(c, d_hist, kIcpMaxHistory) != NDT_OK ||
+            make_pinned(c, h_state, 2, hipHostMallocCoherent) != NDT_OK)
             return fail(c, NDT_ENOMEM, "ICP state allocation failed");
+        c->icp.d_state = std::move(d_state);
+        c->icp.d_hist = std::move(d_hist);
+        c->icp.h_state = std::move(h_state);
     }
     const int N = c->N;
     const int nb = std::max(1, std::min(ceil_div(N, kIcpTeams), kIcpMaxBlocks));
-    TRY(ensure(c, c->icp_x, N)); TRY(ensure(c, c->icp_match, N)); TRY(ensure(c, c->icp_d2, N));
-    TRY(ensure(c, c->icp_part, (size_t)kIcpSums * kIcpMaxBlocks));
-    if (!c->icp_ticket.p) {
-        TRY(ensure(c, c->icp_ticket, 64));
-        HIPCHK(c, hipMemsetAsync(c->icp_ticket.p, 0, c->icp_ticket.cap * sizeof(unsigned), c->stream));
+    TRY(ensure(c, c->icp.x, N)); TRY(ensure(c, c->icp.match, N)); TRY(ensure(c, c->icp.d2, N));
+    TRY(ensure(c, c->icp.part, (size_t)kIcpSums * kIcpMaxBlocks));
+    if (!c->icp.ticket.p) {
+        TRY(ensure(c, c->icp.ticket, 64));
+        HIPCHK(c, hipMemsetAsync(c->icp.ticket.p, 0, c->icp.ticket.cap * sizeof(unsigned), c->stream.get()));
     }
     // X = the source (transformed by the guess in the first pass, unless the guess is the identity)
-    TRY(copy16(c, c->stream, c->icp_x.p, c->source.p, (size_t)N * sizeof(float4)));
-    IcpState* s0 = &c->h_icp[1];
+    TRY(copy16(c, c->stream.get(), c->icp.x.p, c->source.p, (size_t)N * sizeof(float4)));
+    IcpState* s0 = &c->icp.h_state[1];
     std::memset(s0, 0, sizeof(IcpState));
     s0->max_corr2 = p.max_corr_dist * p.max_corr_dist;
     s0->trans_eps = p.trans_eps;
@@ -110,7 +115,7 @@ ndt_status ndt_icp_align(ndt_ctx* c, const ndt_icp_params* prm, const float gues
         identity = identity && v == (k % 5 == 0 ? 1.f : 0.f);
     }
     s0->apply = identity ? 0 : 1;
-    HIPCHK(c, hipMemcpyAsync(c->d_icp, s0, sizeof(IcpState), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->icp.d_state.p, s0, sizeof(IcpState), hipMemcpyHostToDevice, c->stream.get()));
     static const int run_env = [] {
         const char* e = std::getenv("NDT_ICP_RUN");  // A/B runs
         return e ? std::max(1, std::min(64, std::atoi(e))) : kIcpRun;
@@ -119,41 +124,39 @@ ndt_status ndt_icp_align(ndt_ctx* c, const ndt_icp_params* prm, const float gues
     hipGraphExec_t gx = nullptr;
     TRY(icp_graph(c, run, nb, &gx));
     const int max_rounds = std::max(p.max_iter, 1) / run + 2;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->profiling) {
-        HIPCHK(c, hipEventCreate(&e0));
-        HIPCHK(c, hipEventCreate(&e1));
-        HIPCHK(c, hipEventRecord(e0, c->stream));
+    Event e0, e1;  // profiling: timing events around the rounds, released on every return
+    if (c->opt.profiling) {
+        TRY(make_event(c, e0, hipEventDefault));
+        TRY(make_event(c, e1, hipEventDefault));
+        HIPCHK(c, hipEventRecord(e0.get(), c->stream.get()));
     }
     c->have_result = false;
     bool finished = false;
     for (int round = 0; round < max_rounds && !finished; ++round) {
-        HIPCHK(c, hipGraphLaunch(gx, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        finished = c->h_icp[0].done != 0;
+        HIPCHK(c, hipGraphLaunch(gx, c->stream.get()));
+        HIPCHK(c, hipStreamSynchronize(c->stream.get()));
+        finished = c->icp.h_state[0].done != 0;
     }
     if (e0) {
-        HIPCHK(c, hipEventRecord(e1, c->stream));
-        HIPCHK(c, hipEventSynchronize(e1));
+        HIPCHK(c, hipEventRecord(e1.get(), c->stream.get()));
+        HIPCHK(c, hipEventSynchronize(e1.get()));
         float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
+        HIPCHK(c, hipEventElapsedTime(&ms, e0.get(), e1.get()));
         c->ms_align = ms;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
     }
     if (!finished) return fail(c, NDT_EDEVICE, "ICP did not finish within its iteration budget");
     int ix_err = 0;  // the index sort's error bits, as k_fitness reports them through its count
-    HIPCHK(c, hipMemcpy(&ix_err, &c->fit_ix.hdr->pad[0], sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&ix_err, &c->fit_ix.hdr.p->pad[0], sizeof(int), hipMemcpyDeviceToHost));
     if (ix_err) {
         c->fit_valid = false;
         return fail(c, NDT_EDEVICE, "ICP: nearest-neighbour index sort: radix look-back timed out");
     }
-    const IcpState& s = c->h_icp[0];
-    c->icp_hist.resize(std::min(s.hist_count, kIcpMaxHistory));
-    if (!c->icp_hist.empty())
-        HIPCHK(c, hipMemcpy(c->icp_hist.data(), c->d_icp_hist, c->icp_hist.size() * sizeof(IcpRecordDev), hipMemcpyDeviceToHost));
+    const IcpState& s = c->icp.h_state[0];
+    c->icp.hist.resize(std::min(s.hist_count, kIcpMaxHistory));
+    if (!c->icp.hist.empty())
+        HIPCHK(c, hipMemcpy(c->icp.hist.data(), c->icp.d_hist.p, c->icp.hist.size() * sizeof(IcpRecordDev), hipMemcpyDeviceToHost));
     for (int k = 0; k < 16; ++k) {
-        c->icp_final[k] = s.final_tf[k];
+        c->icp.final_tf[k] = s.final_tf[k];
         out->final_tf[k] = s.final_tf[k];
     }
     out->converged = s.converged;
@@ -161,8 +164,8 @@ ndt_status ndt_icp_align(ndt_ctx* c, const ndt_icp_params* prm, const float gues
     out->nr_iterations = s.iterations;
     out->mse = s.mse;
     out->n_pairs = s.pairs;
-    c->icp_n = N;
-    c->last_icp = true;
+    c->icp.n = N;
+    c->icp.last = true;
     c->have_result = true;
     c->align_tgt_gen = c->tgt_gen;
     return NDT_OK;
@@ -170,25 +173,25 @@ ndt_status ndt_icp_align(ndt_ctx* c, const ndt_icp_params* prm, const float gues
 
 ndt_status ndt_icp_history(ndt_ctx* c, ndt_icp_record* out, int cap, int* n_out) {
     if (!c || !n_out || (cap > 0 && !out)) return fail(c, NDT_EINVAL, "bad history args");
-    const int n = std::min((int)c->icp_hist.size(), std::max(cap, 0));
+    const int n = std::min((int)c->icp.hist.size(), std::max(cap, 0));
     for (int i = 0; i < n; ++i) {
-        for (int k = 0; k < 16; ++k) out[i].T[k] = c->icp_hist[i].T[k];
-        out[i].n_pairs = c->icp_hist[i].pairs;
-        out[i].mse = c->icp_hist[i].mse;
-        out[i].state = c->icp_hist[i].conv_state;
+        for (int k = 0; k < 16; ++k) out[i].T[k] = c->icp.hist[i].T[k];
+        out[i].n_pairs = c->icp.hist[i].pairs;
+        out[i].mse = c->icp.hist[i].mse;
+        out[i].state = c->icp.hist[i].conv_state;
     }
-    *n_out = (int)c->icp_hist.size();
+    *n_out = (int)c->icp.hist.size();
     return NDT_OK;
 }
 
 ndt_status ndt_icp_correspondences(ndt_ctx* c, int* index, float* d2, size_t cap, size_t* n_out) {
     if (!c || !n_out) return fail(c, NDT_EINVAL, "null argument");
-    if (!c->icp_n || !c->icp_match.p) return fail(c, NDT_EINVAL, "no ICP align");
+    if (!c->icp.n || !c->icp.match.p) return fail(c, NDT_EINVAL, "no ICP align");
     TRY(set_dev(c));
-    const size_t n = std::min((size_t)c->icp_n, cap);
-    if (index && n) HIPCHK(c, hipMemcpy(index, c->icp_match.p, n * sizeof(int), hipMemcpyDeviceToHost));
-    if (d2 && n) HIPCHK(c, hipMemcpy(d2, c->icp_d2.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    *n_out = (size_t)c->icp_n;
+    const size_t n = std::min((size_t)c->icp.n, cap);
+    if (index && n) HIPCHK(c, hipMemcpy(index, c->icp.match.p, n * sizeof(int), hipMemcpyDeviceToHost));
+    if (d2 && n) HIPCHK(c, hipMemcpy(d2, c->icp.d2.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    *n_out = (size_t)c->icp.n;
     return NDT_OK;
 }
 

@@ -6,7 +6,7 @@ struct ndt_isc {
     ndt_ctx* c = nullptr;
     ndt_isc_params prm{};
     int size = 0;
-    size_t cap = 0;                  // slots allocated
+    SlotArrays mem;                  // the database's arrays
     IscDb db{nullptr, nullptr, nullptr, nullptr, nullptr};
     // pos_arr and travel_distance_arr (the prefix sum is sequential: accumulated here, the device gets the arrays)
     std::vector<double> pos, travel;
@@ -23,46 +23,12 @@ static bool isc_valid_params(const ndt_isc_params* p) {
            !std::isnan(p->geometry_threshold) && !std::isnan(p->intensity_threshold) && !std::isnan(p->z_min) && !std::isnan(p->z_max);
 }
 
-static void isc_free_db(IscDb& db) {
-    if (db.cols) (void)hipFree(db.cols);
-    if (db.zero) (void)hipFree(db.zero);
-    if (db.one) (void)hipFree(db.one);
-    if (db.pos) (void)hipFree(db.pos);
-    if (db.travel) (void)hipFree(db.travel);
-    db = IscDb{nullptr, nullptr, nullptr, nullptr, nullptr};
-}
-
-// Room for one more slot, as the Scan Context database grows: capacity doubles, the stored slots move device to device.
-// The stream is synchronised before the old arrays are freed: launches queued on it may still read them.
+// Room for one more slot, as the Scan Context database grows (reserve_slots)
 static ndt_status isc_reserve(ndt_isc* h, size_t need) {
-    ndt_ctx* c = h->c;
-    if (need <= h->cap) return NDT_OK;
-    const size_t cap = std::max<size_t>(std::max<size_t>(need, 64), h->cap * 2);
     const size_t S = (size_t)h->prm.sectors, colb = S * kIscColBytes, maskb = S * sizeof(unsigned long long);
-    IscDb nd{nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (hipMalloc(&nd.cols, cap * colb) != hipSuccess || hipMalloc(&nd.zero, cap * maskb) != hipSuccess ||
-        hipMalloc(&nd.one, cap * maskb) != hipSuccess || hipMalloc(&nd.pos, cap * 3 * sizeof(double)) != hipSuccess ||
-        hipMalloc(&nd.travel, cap * sizeof(double)) != hipSuccess) {
-        isc_free_db(nd);
-        return fail(c, NDT_ENOMEM, "ISC database allocation failed");
-    }
-    hipError_t e = hipStreamSynchronize(c->stream);
-    const size_t n = (size_t)h->size;
-    if (e == hipSuccess && n) {
-        e = hipMemcpyAsync(nd.cols, h->db.cols, n * colb, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nd.zero, h->db.zero, n * maskb, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nd.one, h->db.one, n * maskb, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nd.pos, h->db.pos, n * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nd.travel, h->db.travel, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    if (e != hipSuccess) {
-        isc_free_db(nd);
-        return fail(c, NDT_EDEVICE, std::string("ISC database growth: ") + hipGetErrorString(e));
-    }
-    isc_free_db(h->db);
-    h->db = nd;
-    h->cap = cap;
+    TRY(reserve_slots(h->c, h->mem, (size_t)h->size, need, {colb, maskb, maskb, 3 * sizeof(double), sizeof(double)}, "ISC"));
+    h->db = IscDb{h->mem.at<unsigned char>(0), h->mem.at<unsigned long long>(1), h->mem.at<unsigned long long>(2), h->mem.at<double>(3),
+                  h->mem.at<double>(4)};
     return NDT_OK;
 }
 
@@ -77,7 +43,7 @@ static ndt_status isc_finish_add(ndt_isc* h, const unsigned* img, const double p
         const double dx = b[0] - p[0], dy = b[1] - p[1], dz = b[2] - p[2];
         travel = h->travel.back() + std::sqrt((dx * dx + dy * dy) + dz * dz);
     }
-    hipLaunchKernelGGL(k_isc_finalize, dim3(1), dim3(kIscBlock), 0, c->stream, img, h->db, h->size, h->prm.rings, h->prm.sectors, p[0], p[1],
+    hipLaunchKernelGGL(k_isc_finalize, dim3(1), dim3(kIscBlock), 0, c->stream.get(), img, h->db, h->size, h->prm.rings, h->prm.sectors, p[0], p[1],
                        p[2], travel);
     HIPCHK(c, hipGetLastError());
     h->pos.insert(h->pos.end(), p, p + 3);
@@ -93,7 +59,7 @@ static ndt_status isc_add_points(ndt_isc* h, const float4* d_pts, size_t n, cons
     TRY(isc_reserve(h, (size_t)h->size + 1));
     const size_t cells = (size_t)kIscMaxSectors * kIscColBytes;
     TRY(ensure(c, h->img, cells));
-    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)h->img.p, 0, cells, c->stream));
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)h->img.p, 0, cells, c->stream.get()));
     if (n) {
         IscGeom g;
         g.rings = h->prm.rings;
@@ -104,7 +70,7 @@ static ndt_status isc_add_points(ndt_isc* h, const float4* d_pts, size_t n, cons
         g.z_min = h->prm.z_min;
         g.z_max = h->prm.z_max;
         const int nb = std::min(ceil_div((long long)n, kIscBlock * kIscMakePerThread), kIscMakeMaxBlocks);
-        hipLaunchKernelGGL(k_isc_make, dim3(nb), dim3(kIscBlock), 0, c->stream, d_pts, (int)n, g, h->img.p);
+        hipLaunchKernelGGL(k_isc_make, dim3(nb), dim3(kIscBlock), 0, c->stream.get(), d_pts, (int)n, g, h->img.p);
     }
     return isc_finish_add(h, h->img.p, pos, index);
 }
@@ -131,12 +97,12 @@ static ndt_status isc_run(ndt_isc* h, const int* d_query, int q0, int q_max, int
     TRY(ensure(c, h->d_res, (size_t)n));
     TRY(ensure(c, h->d_part, (size_t)n * n_chunks));
     const IscDetectArgs a = isc_args(h, n_chunks, pair_j, pair_angle);
-    hipLaunchKernelGGL(k_isc_detect, dim3(n, n_chunks), dim3(kIscBlock), 0, c->stream, h->db, d_query, q0, a, h->d_part.p);
-    hipLaunchKernelGGL(k_isc_reduce, dim3(ceil_div(n, kIscBlock)), dim3(kIscBlock), 0, c->stream, (const IscPartial*)h->d_part.p, d_query, q0, n,
+    hipLaunchKernelGGL(k_isc_detect, dim3(n, n_chunks), dim3(kIscBlock), 0, c->stream.get(), h->db, d_query, q0, a, h->d_part.p);
+    hipLaunchKernelGGL(k_isc_reduce, dim3(ceil_div(n, kIscBlock)), dim3(kIscBlock), 0, c->stream.get(), (const IscPartial*)h->d_part.p, d_query, q0, n,
                        a, h->d_res.p);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, h->d_res.p, (size_t)n * sizeof(ndt_isc_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, h->d_res.p, (size_t)n * sizeof(ndt_isc_result), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     return NDT_OK;
 }
 
@@ -174,8 +140,7 @@ ndt_status ndt_isc_create(ndt_ctx* c, const ndt_isc_params* prm, ndt_isc** out) 
 void ndt_isc_destroy(ndt_isc* h) {
     if (!h) return;
     (void)hipSetDevice(h->c->device);
-    (void)hipStreamSynchronize(h->c->stream);  // queued launches still read the database
-    isc_free_db(h->db);
+    (void)hipStreamSynchronize(h->c->stream.get());  // queued launches still read the database
     delete h;
 }
 
@@ -202,8 +167,8 @@ ndt_status ndt_isc_add(ndt_isc* h, const float* xyzi, size_t n, size_t stride_by
         const float* f = reinterpret_cast<const float*>(base + i * stride_bytes);
         tmp[i] = make_float4(f[0], f[1], f[2], f[intensity_offset]);
     }
-    if (n) HIPCHK(c, hipMemcpyAsync(h->pts.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // tmp is free; the previous add has read h->pts
+    if (n) HIPCHK(c, hipMemcpyAsync(h->pts.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));  // tmp is free; the previous add has read h->pts
     return isc_add_points(h, h->pts.p, n, pos, index);
 }
 
@@ -217,8 +182,8 @@ ndt_status ndt_isc_add_descriptor(ndt_isc* h, const unsigned char* bytes, const 
     std::vector<unsigned char> cols((size_t)S * kIscColBytes, 0);  // sector-major, each column zero-padded
     for (int q = 0; q < R; ++q)
         for (int p = 0; p < S; ++p) cols[(size_t)p * kIscColBytes + q] = bytes[(size_t)q * S + p];
-    HIPCHK(c, hipMemcpyAsync(h->db.cols + (size_t)h->size * cols.size(), cols.data(), cols.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // cols is free
+    HIPCHK(c, hipMemcpyAsync(h->db.cols + (size_t)h->size * cols.size(), cols.data(), cols.size(), hipMemcpyHostToDevice, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));  // cols is free
     return isc_finish_add(h, nullptr, pos, index);
 }
 
@@ -243,7 +208,7 @@ ndt_status ndt_isc_detect_batch(ndt_isc* h, const int* query, int n, ndt_isc_res
     }
     TRY(set_dev(c));
     TRY(ensure(c, h->d_query, (size_t)n));
-    HIPCHK(c, hipMemcpyAsync(h->d_query.p, query, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h->d_query.p, query, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream.get()));
     return isc_run(h, h->d_query.p, 0, q_max, -1, -1, n, out);
 }
 
@@ -278,7 +243,7 @@ ndt_status ndt_isc_get(ndt_isc* h, int index, unsigned char* bytes, double* pos,
     ndt_ctx* c = h->c;
     if (index < 0 || index >= h->size) return fail(c, NDT_EINVAL, "descriptor index out of range");
     TRY(set_dev(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     const size_t k = (size_t)index;
     const int R = h->prm.rings, S = h->prm.sectors;
     if (bytes) {

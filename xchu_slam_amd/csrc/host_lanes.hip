@@ -49,42 +49,38 @@ void LaneWorker::run() {
 }
 
 // the side lanes (fit_stream / ins_stream), created on the first side-lane call, at the lowest stream priority (the
-// main stream, whose target build and align are the scan loop's critical path, has the highest)
+// main stream, whose target build and align are the scan loop's critical path, has the highest).  Built apart and
+// moved into the ctx whole: a step that fails leaves the ctx without side lanes, and the next call starts over.
 static ndt_status side_lanes(ndt_ctx* c) {
-    if (c->fit_stream) return NDT_OK;
+    if (c->lanes.fit_worker) return NDT_OK;
     int least = 0, greatest = 0;
     HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-    if (!c->lane_mask.empty()) {
-        HIPCHK(c, hipExtStreamCreateWithCUMask(&c->fit_stream, (uint32_t)c->lane_mask.size() * 32, c->lane_mask.data()));
-        HIPCHK(c, hipExtStreamCreateWithCUMask(&c->ins_stream, (uint32_t)c->lane_mask.size() * 32, c->lane_mask.data()));
-    } else {
-        HIPCHK(c, hipStreamCreateWithPriority(&c->fit_stream, hipStreamNonBlocking, least));
-        HIPCHK(c, hipStreamCreateWithPriority(&c->ins_stream, hipStreamNonBlocking, least));
-    }
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_main_fit, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_main_ins, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_fit_src, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_fit_tgt, hipEventDisableTiming));
-    if (hipMalloc(&c->d_hdr_ins, sizeof(GridHeader)) != hipSuccess) return fail(c, NDT_ENOMEM, "hipMalloc failed");
-    c->fit_worker = new LaneWorker(c->device, &c->capture_mu);
-    c->ins_worker = new LaneWorker(c->device, &c->capture_mu);
+    SideLanes L;
+    TRY(make_stream(c, L.fit_stream, least));
+    TRY(make_stream(c, L.ins_stream, least));
+    for (Event* e : {&L.ev_main_fit, &L.ev_main_ins, &L.ev_fit_src, &L.ev_fit_tgt, &L.ev_fit, &L.ev_ins})
+        TRY(make_event(c, *e, hipEventDisableTiming));
+    TRY(ensure(c, L.d_hdr_ins, 1));
+    L.ins_worker = std::make_unique<LaneWorker>(c->device, &c->capture_mu);
+    L.fit_worker = std::make_unique<LaneWorker>(c->device, &c->capture_mu);
+    c->lanes = std::move(L);
     return NDT_OK;
 }
 
 // the main stream continues after the fit-lane work that reads what it is about to rewrite: the last query that read the
 // ctx's source (source = true) or the last index build that read the ctx's target points (source = false)
 ndt_status main_after_fit(ndt_ctx* c, bool source) {
-    if (!(source ? c->fit_src_used : c->fit_tgt_used)) return NDT_OK;
+    if (!(source ? c->lanes.fit_src_used : c->lanes.fit_tgt_used)) return NDT_OK;
     std::string msg;
     // every queued fit-lane launch issued; a failure is reported here and cleared (it would otherwise block every later
     // target / source change), and the index it may have left unbuilt is dropped
-    const ndt_status st = c->fit_worker->take_error(&msg);
+    const ndt_status st = c->lanes.fit_worker->take_error(&msg);
     if (st != NDT_OK) {
         c->fit_valid = false;
-        c->fit_pending = false;
+        c->lanes.fit_pending = false;
         return fail(c, st, "getFitnessScore: " + msg);
     }
-    HIPCHK(c, hipStreamWaitEvent(c->stream, source ? c->ev_fit_src : c->ev_fit_tgt, 0));
+    HIPCHK(c, hipStreamWaitEvent(c->stream.get(), source ? c->lanes.ev_fit_src.get() : c->lanes.ev_fit_tgt.get(), 0));
     return NDT_OK;
 }
 
@@ -92,23 +88,23 @@ ndt_status main_after_fit(ndt_ctx* c, bool source) {
 // Builds an NNIndex over n device points (cell = base cell size, doubled by k_header until the block-major key range
 // fits).  Uses the ctx's sort scratch; stream-ordered.
 ndt_status enqueue_nn_index(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, float cell, NNIndex& ix, bool want_idx) {
-    TRY(enqueue_bin_and_sort(c, L, pts, n, dense, ix.hdr, cell, 1));
+    TRY(enqueue_bin_and_sort(c, L, pts, n, dense, ix.hdr.p, cell, 1));
     TRY(ensure(c, ix.pts, std::max(n, 1))); TRY(ensure(c, ix.keys, std::max(n, 1))); TRY(ensure(c, ix.start, (size_t)n + 1));
     if (want_idx) TRY(ensure(c, ix.idx, std::max(n, 1)));
     const int nb = std::max(1, std::min(ceil_div(n, kBlock), 4096));
     hipLaunchKernelGGL(k_fit_gather, dim3(nb), dim3(kBlock), 0, L.st, pts, L.s.k0.p, L.s.k1.p, L.s.v0.p, L.s.v1.p,
-                       L.s.seg_start.p, n, ix.hdr, ix.pts.p, ix.keys.p, ix.start.p, want_idx ? ix.idx.p : nullptr);
+                       L.s.seg_start.p, n, ix.hdr.p, ix.pts.p, ix.keys.p, ix.start.p, want_idx ? ix.idx.p : nullptr);
     // occupied blocks: flags -> exclusive scan -> block table + 513 cell offsets per occupied block
     const size_t max_occ = (size_t)std::max(1, std::min(n, kFitMaxBlocks));
     TRY(ensure(c, L.s.flags, std::max(n, 1))); TRY(ensure(c, L.s.cloud_idx, std::max(n, 1)));
     TRY(ensure(c, ix.blk, (size_t)kFitMaxBlocks)); TRY(ensure(c, ix.off, max_occ * (kFitBlockCells + 1)));
     const int nb_pts = std::max(1, ceil_div(n, kBlock));
-    hipLaunchKernelGGL(k_fit_block_flags, dim3(nb_pts), dim3(kBlock), 0, L.st, ix.keys.p, ix.hdr, L.s.flags.p);
-    TRY(enqueue_scan(c, L, L.s.flags.p, std::max(n, 1), &ix.hdr->n_leaves, L.s.cloud_idx.p, &ix.hdr->n_blocks_occ, ix.hdr));
+    hipLaunchKernelGGL(k_fit_block_flags, dim3(nb_pts), dim3(kBlock), 0, L.st, ix.keys.p, ix.hdr.p, L.s.flags.p);
+    TRY(enqueue_scan(c, L, L.s.flags.p, std::max(n, 1), &ix.hdr.p->n_leaves, L.s.cloud_idx.p, &ix.hdr.p->n_blocks_occ, ix.hdr.p));
     hipLaunchKernelGGL(k_fit_block_clear, dim3(std::max(1, std::min(kFitMaxBlocks / kBlock, 256))), dim3(kBlock), 0, L.st,
-                       ix.blk.p, ix.hdr);
+                       ix.blk.p, ix.hdr.p);
     hipLaunchKernelGGL(k_fit_tables, dim3(nb_pts), dim3(kBlock), 0, L.st, ix.keys.p, ix.start.p, L.s.flags.p,
-                       L.s.cloud_idx.p, ix.hdr, ix.blk.p, ix.off.p);
+                       L.s.cloud_idx.p, ix.hdr.p, ix.blk.p, ix.off.p);
     HIPCHK(c, hipGetLastError());
     return NDT_OK;
 }
@@ -117,12 +113,12 @@ ndt_status enqueue_nn_index(ndt_ctx* c, Lane L, const float4* pts, int n, int de
 // ahead of the voxel build, so the two builds run side by side); issued by the lane's host thread
 ndt_status ensure_fit_index(ndt_ctx* c) {
     TRY(side_lanes(c));
-    if (c->fit_worker->failed()) {
+    if (c->lanes.fit_worker->failed()) {
         // a fit-lane job failed (possibly this index's build): report it now instead of querying a half-built index
         std::string msg;
-        const ndt_status st = c->fit_worker->take_error(&msg);
+        const ndt_status st = c->lanes.fit_worker->take_error(&msg);
         c->fit_valid = false;
-        c->fit_pending = false;
+        c->lanes.fit_pending = false;
         return fail(c, st, "getFitnessScore: " + msg);
     }
     if (c->fit_valid) return NDT_OK;
@@ -130,19 +126,19 @@ ndt_status ensure_fit_index(ndt_ctx* c) {
     const int M = c->M, dense = c->target_dense;
     const float res = c->prm.resolution;
     if (!c->tgt_ev_valid) {  // the first index of this ctx: behind everything queued so far (the build included)
-        HIPCHK(c, hipEventRecord(c->ev_tgt, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_tgt.get(), c->stream.get()));
         c->tgt_ev_valid = true;
     }
     c->fit_ix_gen = c->tgt_gen;
-    const bool want_idx = c->icp_used;
-    c->fit_worker->post([c, pts, M, dense, res, want_idx]() -> ndt_status {
-        HIPCHK(c, hipStreamWaitEvent(c->fit_stream, c->ev_tgt, 0));
+    const bool want_idx = c->icp.used;
+    c->lanes.fit_worker->post([c, pts, M, dense, res, want_idx]() -> ndt_status {
+        HIPCHK(c, hipStreamWaitEvent(c->lanes.fit_stream.get(), c->ev_tgt.get(), 0));
         // target points binned in 8x8x8-cell blocks (block-major keys, same stable radix sort as the voxel build)
-        TRY(enqueue_nn_index(c, Lane{c->fit_stream, c->s_fit}, pts, M, dense, res, c->fit_ix, want_idx));
-        HIPCHK(c, hipEventRecord(c->ev_fit_tgt, c->fit_stream));
+        TRY(enqueue_nn_index(c, Lane{c->lanes.fit_stream.get(), c->lanes.s_fit}, pts, M, dense, res, c->fit_ix, want_idx));
+        HIPCHK(c, hipEventRecord(c->lanes.ev_fit_tgt.get(), c->lanes.fit_stream.get()));
         return NDT_OK;
     });
-    c->fit_tgt_used = true;
+    c->lanes.fit_tgt_used = true;
     c->fit_valid = true;
     return NDT_OK;
 }
@@ -157,35 +153,32 @@ static ndt_status fitness_enqueue(ndt_ctx* c, const float* T, double max_range, 
     for (int k = 0; k < 16; ++k) Tm.m[k] = T ? T[k] : (c->have_result ? last_final(c)[k] : (k % 5 == 0 ? 1.f : 0.f));
     // the query runs on the fit lane behind the main stream's work so far (the source copy, the align whose transform
     // it applies: the marker is recorded here, on the caller's thread) and beside whatever the main stream queues next
-    if (c->lanes_marked & 1) c->lanes_marked &= ~1;  // the caller's mark (ndt_side_lanes_mark)
-    else HIPCHK(c, hipEventRecord(c->ev_main_fit, c->stream));
-    c->fit_worker->post([c, Tm, src, N, max_range, ctx_source]() -> ndt_status {
-        HIPCHK(c, hipStreamWaitEvent(c->fit_stream, c->ev_main_fit, 0));
+    if (c->lanes.marked & 1) c->lanes.marked &= ~1;  // the caller's mark (ndt_side_lanes_mark)
+    else HIPCHK(c, hipEventRecord(c->lanes.ev_main_fit.get(), c->stream.get()));
+    c->lanes.fit_worker->post([c, Tm, src, N, max_range, ctx_source]() -> ndt_status {
+        HIPCHK(c, hipStreamWaitEvent(c->lanes.fit_stream.get(), c->lanes.ev_main_fit.get(), 0));
         // 16-lane team per query; the grid capped at 32 Ki workgroups (measured caps 8192 / 2048 / 1024 / 512 of 256-thread
         // workgroups: 89.4 / 85.9 / 90.7 / 128.9 us on C3)
-        static const int grid_cap = [] {
-            const char* e = std::getenv("NDT_FIT_GRID");  // A/B runs
-            return e ? std::max(1, std::atoi(e)) : 8192 * (256 / NDT_FIT_BLOCK);
-        }();
+        constexpr int grid_cap = 8192 * (256 / NDT_FIT_BLOCK);
         const int nb = std::max(1, std::min(ceil_div(N, NDT_FIT_BLOCK / NDT_FIT_TEAM), grid_cap));
         const int ngrp = ceil_div(nb, kFitGroup);
         TRY(ensure(c, c->fit_sum, nb + ngrp)); TRY(ensure(c, c->fit_cnt, nb + ngrp)); TRY(ensure(c, c->fit_d2, N));
         const size_t n_ticket = (size_t)kFitTicketStride * (1 + ngrp);
         if (c->fit_ticket.cap < n_ticket) {
             TRY(ensure(c, c->fit_ticket, n_ticket));
-            HIPCHK(c, hipMemsetAsync(c->fit_ticket.p, 0, c->fit_ticket.cap * sizeof(unsigned), c->fit_stream));
+            HIPCHK(c, hipMemsetAsync(c->fit_ticket.p, 0, c->fit_ticket.cap * sizeof(unsigned), c->lanes.fit_stream.get()));
         }
         // the last workgroup sums the partials and writes (sum, count) straight into the pinned result slots
-        hipLaunchKernelGGL(k_fitness, dim3(nb), dim3(NDT_FIT_BLOCK), 0, c->fit_stream, src, N, Tm, c->fit_ix.hdr, c->fit_ix.blk.p,
+        hipLaunchKernelGGL(k_fitness, dim3(nb), dim3(NDT_FIT_BLOCK), 0, c->lanes.fit_stream.get(), src, N, Tm, c->fit_ix.hdr.p, c->fit_ix.blk.p,
                            c->fit_ix.off.p, c->fit_ix.pts.p, max_range, c->fit_d2.p, c->fit_sum.p, c->fit_cnt.p, c->fit_ticket.p,
                            &c->h_async->fit_sum, &c->h_async->fit_cnt);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev_fit, c->fit_stream));
-        if (ctx_source) HIPCHK(c, hipEventRecord(c->ev_fit_src, c->fit_stream));
+        HIPCHK(c, hipEventRecord(c->lanes.ev_fit.get(), c->lanes.fit_stream.get()));
+        if (ctx_source) HIPCHK(c, hipEventRecord(c->lanes.ev_fit_src.get(), c->lanes.fit_stream.get()));
         return NDT_OK;
     });
-    if (ctx_source) c->fit_src_used = true;
-    c->fit_pending = true;
+    if (ctx_source) c->lanes.fit_src_used = true;
+    c->lanes.fit_pending = true;
     c->fit_n = N;
     return NDT_OK;
 }
@@ -223,7 +216,7 @@ ndt_status ndt_fitness_score_async_aligned(ndt_ctx* c, double max_range, const f
         for (int k = 0; k < 16; ++k) T[k] = last_final(c)[k];
         return fitness_enqueue(c, T, max_range, reinterpret_cast<const float4*>(d_src4), (int)n, false);
     }
-    if (c->fit_ix_gen != c->align_tgt_gen || !c->fit_worker || c->fit_worker->failed())
+    if (c->fit_ix_gen != c->align_tgt_gen || !c->lanes.fit_worker || c->lanes.fit_worker->failed())
         return fail(c, NDT_EINVAL, "getFitnessScore: the aligned target's index was not queued before setInputTarget");
     float T[16];
     for (int k = 0; k < 16; ++k) T[k] = last_final(c)[k];
@@ -241,15 +234,15 @@ ndt_status ndt_fitness_score_result(ndt_ctx* c, double* out) {
     if (!c || !out) return fail(c, NDT_EINVAL, "null argument");
     std::string msg;
     // a failed fit-lane job is taken (and cleared) even when no query is pending, so that it cannot stay stuck
-    const ndt_status st = c->fit_worker ? c->fit_worker->take_error(&msg) : NDT_OK;  // every fit-lane job issued
-    if (st == NDT_OK && !c->fit_pending) return fail(c, NDT_EINVAL, "no fitness score enqueued");
+    const ndt_status st = c->lanes.fit_worker ? c->lanes.fit_worker->take_error(&msg) : NDT_OK;  // every fit-lane job issued
+    if (st == NDT_OK && !c->lanes.fit_pending) return fail(c, NDT_EINVAL, "no fitness score enqueued");
     TRY(set_dev(c));
     if (st != NDT_OK) {
-        c->fit_pending = false;
+        c->lanes.fit_pending = false;
         c->fit_valid = false;  // the index may not have been built
         return fail(c, st, "getFitnessScore: " + msg);
     }
-    HIPCHK(c, hipEventSynchronize(c->ev_fit));
+    HIPCHK(c, hipEventSynchronize(c->lanes.ev_fit.get()));
     const double sum = c->h_async->fit_sum;
     const long long cnt = c->h_async->fit_cnt;
     if (cnt < 0) {
@@ -266,10 +259,10 @@ ndt_status ndt_fitness_score(ndt_ctx* c, const float T[16], double max_range, do
     TRY(ndt_fitness_score_async(c, T, max_range));
     if (nn_d2) {
         std::string msg;
-        const ndt_status st = c->fit_worker->drain(&msg);  // the query has been issued (its failure is reported below)
+        const ndt_status st = c->lanes.fit_worker->drain(&msg);  // the query has been issued (its failure is reported below)
         if (st == NDT_OK) {
-            HIPCHK(c, hipMemcpyAsync(nn_d2, c->fit_d2.p, (size_t)c->fit_n * sizeof(float), hipMemcpyDeviceToHost, c->fit_stream));
-            HIPCHK(c, hipStreamSynchronize(c->fit_stream));
+            HIPCHK(c, hipMemcpyAsync(nn_d2, c->fit_d2.p, (size_t)c->fit_n * sizeof(float), hipMemcpyDeviceToHost, c->lanes.fit_stream.get()));
+            HIPCHK(c, hipStreamSynchronize(c->lanes.fit_stream.get()));
         }
     }
     return ndt_fitness_score_result(c, out);
@@ -281,42 +274,42 @@ ndt_status ndt_keyframe_insert_async(ndt_ctx* c, const float T[16], const float*
         return fail(c, NDT_EINVAL, "bad keyframe insert args");
     TRY(set_dev(c));
     TRY(side_lanes(c));
-    c->ins_n_in = n;
-    c->ins_pending = true;
+    c->lanes.ins_n_in = n;
+    c->lanes.ins_pending = true;
     // the insertion lane: behind the main stream's work so far (whatever wrote the scan or grew the maps; the marker is
     // recorded here, on the caller's thread), beside what the main stream queues next; its own binning header and sort
     // scratch, its launches issued by the lane's host thread
-    hipEvent_t ev_main = c->ev_main_ins;
-    if (c->lanes_marked & 2) {  // the caller's mark (ndt_side_lanes_mark)
-        c->lanes_marked &= ~2;
-        ev_main = c->ev_main_fit;
+    hipEvent_t ev_main = c->lanes.ev_main_ins.get();
+    if (c->lanes.marked & 2) {  // the caller's mark (ndt_side_lanes_mark)
+        c->lanes.marked &= ~2;
+        ev_main = c->lanes.ev_main_fit.get();
     } else {
-        HIPCHK(c, hipEventRecord(c->ev_main_ins, c->stream));
+        HIPCHK(c, hipEventRecord(c->lanes.ev_main_ins.get(), c->stream.get()));
     }
     Mat4f Tm;
     for (int k = 0; k < 16; ++k) Tm.m[k] = T[k];
     const float4* scan = reinterpret_cast<const float4*>(d_scan4);
     float4* dst_a = reinterpret_cast<float4*>(d_map_a) + n_a;
     float4* dst_b = reinterpret_cast<float4*>(d_map_b) + n_b;
-    c->ins_worker->post([c, Tm, scan, n, leaf, dst_a, dst_b, ev_main]() -> ndt_status {
+    c->lanes.ins_worker->post([c, Tm, scan, n, leaf, dst_a, dst_b, ev_main]() -> ndt_status {
         if (n == 0) {
-            HIPCHK(c, hipStreamSynchronize(c->ins_stream));  // no earlier insertion still writes the pinned header
+            HIPCHK(c, hipStreamSynchronize(c->lanes.ins_stream.get()));  // no earlier insertion still writes the pinned header
             std::memset(&c->h_async->ins_hdr, 0, sizeof(GridHeader));
             c->h_async->ins_hdr.empty = 1;
-            HIPCHK(c, hipEventRecord(c->ev_ins, c->ins_stream));
+            HIPCHK(c, hipEventRecord(c->lanes.ev_ins.get(), c->lanes.ins_stream.get()));
             return NDT_OK;
         }
-        const Lane L{c->ins_stream, c->s_ins};
+        const Lane L{c->lanes.ins_stream.get(), c->lanes.s_ins};
         HIPCHK(c, hipStreamWaitEvent(L.st, ev_main, 0));
-        TRY(ensure(c, c->ins_tr, n)); TRY(ensure(c, c->ins_ds, n));
-        hipLaunchKernelGGL(k_transform_mat, dim3(ceil_div((long long)n, kBlock)), dim3(kBlock), 0, L.st, scan, (int)n, Tm, c->ins_tr.p);
-        TRY(enqueue_bin_and_sort(c, L, c->ins_tr.p, (int)n, 1, c->d_hdr_ins, leaf));
-        TRY(enqueue_downsample_finalize(c, L, c->d_hdr_ins, c->ins_tr.p, (int)n, c->ins_ds.p));
+        TRY(ensure(c, c->lanes.ins_tr, n)); TRY(ensure(c, c->lanes.ins_ds, n));
+        hipLaunchKernelGGL(k_transform_mat, dim3(ceil_div((long long)n, kBlock)), dim3(kBlock), 0, L.st, scan, (int)n, Tm, c->lanes.ins_tr.p);
+        TRY(enqueue_bin_and_sort(c, L, c->lanes.ins_tr.p, (int)n, 1, c->lanes.d_hdr_ins.p, leaf));
+        TRY(enqueue_downsample_finalize(c, L, c->lanes.d_hdr_ins.p, c->lanes.ins_tr.p, (int)n, c->lanes.ins_ds.p));
         hipLaunchKernelGGL(k_append2, dim3(std::max(1, std::min(ceil_div((long long)n, kBlock), 1024))), dim3(kBlock), 0, L.st,
-                           c->ins_ds.p, c->ins_tr.p, (int)n, c->d_hdr_ins, dst_a, dst_b);
+                           c->lanes.ins_ds.p, c->lanes.ins_tr.p, (int)n, c->lanes.d_hdr_ins.p, dst_a, dst_b);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(&c->h_async->ins_hdr, c->d_hdr_ins, sizeof(GridHeader), hipMemcpyDeviceToHost, L.st));
-        HIPCHK(c, hipEventRecord(c->ev_ins, L.st));
+        HIPCHK(c, hipMemcpyAsync(&c->h_async->ins_hdr, c->lanes.d_hdr_ins.p, sizeof(GridHeader), hipMemcpyDeviceToHost, L.st));
+        HIPCHK(c, hipEventRecord(c->lanes.ev_ins.get(), L.st));
         return NDT_OK;
     });
     return NDT_OK;
@@ -326,25 +319,25 @@ ndt_status ndt_side_lanes_mark(ndt_ctx* c) {
     if (!c) return NDT_EINVAL;
     TRY(set_dev(c));
     TRY(side_lanes(c));
-    HIPCHK(c, hipEventRecord(c->ev_main_fit, c->stream));
-    c->lanes_marked = 3;
+    HIPCHK(c, hipEventRecord(c->lanes.ev_main_fit.get(), c->stream.get()));
+    c->lanes.marked = 3;
     return NDT_OK;
 }
 
 ndt_status ndt_keyframe_insert_result(ndt_ctx* c, size_t* n_inserted) {
     if (!c || !n_inserted) return fail(c, NDT_EINVAL, "null argument");
-    if (!c->ins_pending) return fail(c, NDT_EINVAL, "no keyframe insertion enqueued");
+    if (!c->lanes.ins_pending) return fail(c, NDT_EINVAL, "no keyframe insertion enqueued");
     TRY(set_dev(c));
     std::string msg;
-    const ndt_status st = c->ins_worker->take_error(&msg);  // the insertion has been issued
+    const ndt_status st = c->lanes.ins_worker->take_error(&msg);  // the insertion has been issued
     if (st != NDT_OK) {
-        c->ins_pending = false;
+        c->lanes.ins_pending = false;
         return fail(c, st, "keyframe insertion: " + msg);
     }
-    HIPCHK(c, hipEventSynchronize(c->ev_ins));
+    HIPCHK(c, hipEventSynchronize(c->lanes.ev_ins.get()));
     const GridHeader& h = c->h_async->ins_hdr;
     if (h.pad[0]) return fail(c, NDT_EDEVICE, "keyframe insertion: VoxelGrid sort: radix look-back timed out");
-    *n_inserted = h.overflow ? c->ins_n_in : (h.empty ? 0 : (size_t)h.n_leaves);
+    *n_inserted = h.overflow ? c->lanes.ins_n_in : (h.empty ? 0 : (size_t)h.n_leaves);
     return h.overflow ? NDT_EOVERFLOW : NDT_OK;
 }
 

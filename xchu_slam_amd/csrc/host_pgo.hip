@@ -77,7 +77,7 @@ ndt_status ndt_pgo_create(ndt_ctx* c, const ndt_pgo_params* prm, ndt_pgo** out) 
 void ndt_pgo_destroy(ndt_pgo* g) {
     if (!g) return;
     (void)hipSetDevice(g->c->device);
-    (void)hipStreamSynchronize(g->c->stream);
+    (void)hipStreamSynchronize(g->c->stream.get());
     delete g;
 }
 
@@ -163,9 +163,9 @@ ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
     TRY(ensure(c, g->d_i32, ints.size()));
     TRY(ensure(c, g->d_hist, (size_t)g->prm.max_iter + 1));
     TRY(ensure(c, g->d_out, 1));
-    HIPCHK(c, hipMemcpyAsync(g->d_f64.p, in.data(), n_in * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(g->d_i32.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(g->d_out.p, 0, sizeof(PgoOut), c->stream));
+    HIPCHK(c, hipMemcpyAsync(g->d_f64.p, in.data(), n_in * sizeof(double), hipMemcpyHostToDevice, c->stream.get()));
+    HIPCHK(c, hipMemcpyAsync(g->d_i32.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice, c->stream.get()));
+    HIPCHK(c, hipMemsetAsync(g->d_out.p, 0, sizeof(PgoOut), c->stream.get()));
     PgoGraph d;
     d.n = (int)n;
     d.m = (int)m;
@@ -208,11 +208,11 @@ ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
         a.sig_prior[i] = std::sqrt(g->prm.prior_var[i]);
         a.sig_odom[i] = std::sqrt(g->prm.odom_var[i]);
     }
-    hipLaunchKernelGGL(k_pgo_optimize, dim3(1), dim3(kPgoBlock), 0, c->stream, d, a);
+    hipLaunchKernelGGL(k_pgo_optimize, dim3(1), dim3(kPgoBlock), 0, c->stream.get(), d, a);
     HIPCHK(c, hipGetLastError());
     PgoOut o;
-    HIPCHK(c, hipMemcpyAsync(&o, g->d_out.p, sizeof o, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(&o, g->d_out.p, sizeof o, hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     if (o.status == kPgoNearPi) {
         const std::string what = o.bad == 0 ? "the prior" : o.bad < (int)n ? "odometry edge " + std::to_string(o.bad - 1) + " -> " + std::to_string(o.bad)
                                                                             : "between factor " + std::to_string(o.bad - (int)n);

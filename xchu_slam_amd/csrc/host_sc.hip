@@ -6,7 +6,7 @@ struct ndt_sc {
     ndt_ctx* c = nullptr;
     ndt_sc_params prm{};
     int size = 0;
-    size_t cap = 0;                 // slots allocated
+    SlotArrays mem;                 // the database's arrays
     ScDb db{nullptr, nullptr, nullptr, nullptr};
     DevBuf<unsigned> bins;          // k_sc_make's merged bin images of the descriptor being added
     DevBuf<float4> pts;             // ndt_sc_add's upload
@@ -22,43 +22,48 @@ static bool sc_valid_params(const ndt_sc_params* p) {
            p->num_exclude_recent >= 0 && p->tree_making_period >= 1 && !std::isnan(p->dist_thres);
 }
 
-static void sc_free_db(ScDb& db) {
-    if (db.desc) (void)hipFree(db.desc);
-    if (db.ringkey) (void)hipFree(db.ringkey);
-    if (db.sectorkey) (void)hipFree(db.sectorkey);
-    if (db.colnorm) (void)hipFree(db.colnorm);
-    db = ScDb{nullptr, nullptr, nullptr, nullptr};
+namespace ndt::host {
+
+// Room for `need` slots in a database that stores `size`, contents kept: capacity 64, then doubling; one device block,
+// each array (slot_bytes[k] per slot) at a 256-byte boundary of it; the stored slots move device to device.  A growth
+// that fails leaves the database as it was.  The stream is synchronised before the copies (launches queued on it
+// may still write the old block) and again before the old block is released.
+ndt_status reserve_slots(ndt_ctx* c, SlotArrays& a, size_t size, size_t need, std::initializer_list<size_t> slot_bytes, const char* what) {
+    if (need <= a.cap) return NDT_OK;
+    const size_t cap = std::max<size_t>(std::max<size_t>(need, 64), a.cap * 2);
+    std::vector<size_t> off;
+    size_t total = 0;
+    for (size_t b : slot_bytes) {
+        off.push_back(total);
+        total += (cap * b + 255) / 256 * 256;
+    }
+    DevBuf<char> blk;  // the new block; after the swap below the previous one, released on return
+    if (hipMalloc(&blk.p, total) != hipSuccess) {
+        blk.p = nullptr;
+        return fail(c, NDT_ENOMEM, std::string(what) + " database allocation failed");
+    }
+    blk.cap = total;
+    hipError_t e = hipStreamSynchronize(c->stream.get());
+    size_t k = 0;
+    for (size_t b : slot_bytes) {
+        if (e == hipSuccess && size) e = hipMemcpyAsync(blk.p + off[k], a.arr[k], size * b, hipMemcpyDeviceToDevice, c->stream.get());
+        ++k;
+    }
+    if (e == hipSuccess && size) e = hipStreamSynchronize(c->stream.get());
+    if (e != hipSuccess) return fail(c, NDT_EDEVICE, std::string(what) + " database growth: " + hipGetErrorString(e));
+    std::swap(a.block, blk);
+    a.arr.clear();
+    for (size_t o : off) a.arr.push_back(a.block.p + o);
+    a.cap = cap;
+    return NDT_OK;
 }
 
-// Room for one more slot: capacity doubles, the stored slots move device to device.  The stream is synchronised before
-// the old arrays are freed: launches queued on it may still read them.
+}  // namespace ndt::host
+
 static ndt_status sc_reserve(ndt_sc* sc, size_t need) {
-    ndt_ctx* c = sc->c;
-    if (need <= sc->cap) return NDT_OK;
-    const size_t cap = std::max<size_t>(std::max<size_t>(need, 64), sc->cap * 2);
-    ScDb nd{nullptr, nullptr, nullptr, nullptr};
-    if (hipMalloc(&nd.desc, cap * kScBins * sizeof(double)) != hipSuccess || hipMalloc(&nd.ringkey, cap * kScRings * sizeof(float)) != hipSuccess ||
-        hipMalloc(&nd.sectorkey, cap * kScSectors * sizeof(double)) != hipSuccess ||
-        hipMalloc(&nd.colnorm, cap * kScSectors * sizeof(double)) != hipSuccess) {
-        sc_free_db(nd);
-        return fail(c, NDT_ENOMEM, "Scan Context database allocation failed");
-    }
-    hipError_t e = hipStreamSynchronize(c->stream);
-    const size_t n = (size_t)sc->size;
-    if (e == hipSuccess && n) {
-        e = hipMemcpyAsync(nd.desc, sc->db.desc, n * kScBins * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nd.ringkey, sc->db.ringkey, n * kScRings * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nd.sectorkey, sc->db.sectorkey, n * kScSectors * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nd.colnorm, sc->db.colnorm, n * kScSectors * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    if (e != hipSuccess) {
-        sc_free_db(nd);
-        return fail(c, NDT_EDEVICE, std::string("Scan Context database growth: ") + hipGetErrorString(e));
-    }
-    sc_free_db(sc->db);
-    sc->db = nd;
-    sc->cap = cap;
+    TRY(reserve_slots(sc->c, sc->mem, (size_t)sc->size, need,
+                      {kScBins * sizeof(double), kScRings * sizeof(float), kScSectors * sizeof(double), kScSectors * sizeof(double)}, "Scan Context"));
+    sc->db = ScDb{sc->mem.at<double>(0), sc->mem.at<float>(1), sc->mem.at<double>(2), sc->mem.at<double>(3)};
     return NDT_OK;
 }
 
@@ -67,12 +72,12 @@ static ndt_status sc_add_points(ndt_sc* sc, const float4* d_pts, size_t n, int* 
     if (n > 0x7fffffffULL) return fail(c, NDT_EINVAL, "cloud too large");
     TRY(sc_reserve(sc, (size_t)sc->size + 1));
     TRY(ensure(c, sc->bins, kScBins));
-    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)sc->bins.p, (int)sc_image(kScNoPoint), kScBins, c->stream));
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)sc->bins.p, (int)sc_image(kScNoPoint), kScBins, c->stream.get()));
     if (n) {
         const int nb = std::min(ceil_div((long long)n, kScBlock * kScMakePerThread), kScMakeMaxBlocks);
-        hipLaunchKernelGGL(k_sc_make, dim3(nb), dim3(kScBlock), 0, c->stream, d_pts, (int)n, sc->bins.p);
+        hipLaunchKernelGGL(k_sc_make, dim3(nb), dim3(kScBlock), 0, c->stream.get(), d_pts, (int)n, sc->bins.p);
     }
-    hipLaunchKernelGGL(k_sc_finalize, dim3(1), dim3(kScBlock), 0, c->stream, sc->bins.p, sc->db, sc->size);
+    hipLaunchKernelGGL(k_sc_finalize, dim3(1), dim3(kScBlock), 0, c->stream.get(), sc->bins.p, sc->db, sc->size);
     HIPCHK(c, hipGetLastError());
     if (index) *index = sc->size;
     ++sc->size;
@@ -88,10 +93,10 @@ static ndt_status sc_run(ndt_sc* sc, const int* d_query, const int* d_nsearch, i
     a.radius = (int)std::round(0.5 * sc->prm.search_ratio * kScSectors);
     a.dist_thres = sc->prm.dist_thres;
     a.pair_j = pair_j;
-    hipLaunchKernelGGL(k_sc_detect, dim3(n), dim3(kScBlock), 0, c->stream, sc->db, d_query, d_nsearch, q0, ns0, a, sc->d_res.p);
+    hipLaunchKernelGGL(k_sc_detect, dim3(n), dim3(kScBlock), 0, c->stream.get(), sc->db, d_query, d_nsearch, q0, ns0, a, sc->d_res.p);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, sc->d_res.p, (size_t)n * sizeof(ndt_sc_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, sc->d_res.p, (size_t)n * sizeof(ndt_sc_result), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     return NDT_OK;
 }
 
@@ -125,8 +130,7 @@ ndt_status ndt_sc_create(ndt_ctx* c, const ndt_sc_params* prm, ndt_sc** out) {
 void ndt_sc_destroy(ndt_sc* sc) {
     if (!sc) return;
     (void)hipSetDevice(sc->c->device);
-    (void)hipStreamSynchronize(sc->c->stream);  // queued launches still read the database
-    sc_free_db(sc->db);
+    (void)hipStreamSynchronize(sc->c->stream.get());  // queued launches still read the database
     delete sc;
 }
 
@@ -160,9 +164,9 @@ ndt_status ndt_sc_add_descriptor(ndt_sc* sc, const double desc[1200], int* index
     if (!desc) return fail(c, NDT_EINVAL, "null argument");
     TRY(set_dev(c));
     TRY(sc_reserve(sc, (size_t)sc->size + 1));
-    HIPCHK(c, hipMemcpyAsync(sc->db.desc + (size_t)sc->size * kScBins, desc, kScBins * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's array is free on return
-    hipLaunchKernelGGL(k_sc_finalize, dim3(1), dim3(kScBlock), 0, c->stream, (const unsigned*)nullptr, sc->db, sc->size);
+    HIPCHK(c, hipMemcpyAsync(sc->db.desc + (size_t)sc->size * kScBins, desc, kScBins * sizeof(double), hipMemcpyHostToDevice, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));  // the caller's array is free on return
+    hipLaunchKernelGGL(k_sc_finalize, dim3(1), dim3(kScBlock), 0, c->stream.get(), (const unsigned*)nullptr, sc->db, sc->size);
     HIPCHK(c, hipGetLastError());
     if (index) *index = sc->size;
     ++sc->size;
@@ -194,8 +198,8 @@ ndt_status ndt_sc_detect_batch(ndt_sc* sc, const int* query, const int* n_search
     TRY(set_dev(c));
     TRY(ensure(c, sc->d_query, (size_t)n));
     TRY(ensure(c, sc->d_nsearch, (size_t)n));
-    HIPCHK(c, hipMemcpyAsync(sc->d_query.p, query, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sc->d_nsearch.p, n_search, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sc->d_query.p, query, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream.get()));
+    HIPCHK(c, hipMemcpyAsync(sc->d_nsearch.p, n_search, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream.get()));
     return sc_run(sc, sc->d_query.p, sc->d_nsearch.p, 0, 0, -1, n, out);
 }
 
@@ -216,7 +220,7 @@ ndt_status ndt_sc_get(ndt_sc* sc, int index, double* desc, float* ringkey, doubl
     ndt_ctx* c = sc->c;
     if (index < 0 || index >= sc->size) return fail(c, NDT_EINVAL, "descriptor index out of range");
     TRY(set_dev(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     const size_t k = (size_t)index;
     if (desc) HIPCHK(c, hipMemcpy(desc, sc->db.desc + k * kScBins, kScBins * sizeof(double), hipMemcpyDeviceToHost));
     if (ringkey) HIPCHK(c, hipMemcpy(ringkey, sc->db.ringkey + k * kScRings, kScRings * sizeof(float), hipMemcpyDeviceToHost));

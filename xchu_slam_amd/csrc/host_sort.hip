@@ -7,7 +7,7 @@ namespace ndt::host {
 // launch context of one single-pass scan over nb tiles (look-back words grown and zeroed on demand; the epoch tag
 // makes words of earlier launches stale, so they are never cleared again)
 ndt_status scan_ctx(ndt_ctx* c, Lane L, int nb, ScanCtx* sc) {
-    sc->tickets = c->tile_tickets ? 1 : 0;
+    sc->tickets = c->opt.tile_tickets ? 1 : 0;
     if ((size_t)nb > L.s.scan_status.cap) {
         TRY(ensure(c, L.s.scan_status, (size_t)nb));
         HIPCHK(c, hipMemsetAsync(L.s.scan_status.p, 0, L.s.scan_status.cap * sizeof(unsigned long long), L.st));
@@ -53,7 +53,7 @@ void launch_radix_pass(const ndt_ctx* c, Lane L, int items, int nb, int* k0, int
                        const GridHeader* h, GridHeader* herr, int last_pass) {
     auto* kern = items == 4 ? k_radix_onesweep<4> : items == 16 ? k_radix_onesweep<16> : k_radix_onesweep<24>;
     hipLaunchKernelGGL(kern, dim3(nb), dim3(kBlock), 0, L.st, k0, v0, k1, v1, n, pass, h, L.s.radix_aux.p, L.s.radix_status.p, nb,
-                       herr, last_pass, c->tile_tickets ? 1 : 0);
+                       herr, last_pass, c->opt.tile_tickets ? 1 : 0);
 }
 
 // Radix passes a main-stream sort against the target grid launches (target build, merge-extended build, source order):
@@ -63,7 +63,7 @@ void launch_radix_pass(const ndt_ctx* c, Lane L, int items, int nb, int* k0, int
 // build re-run with four (align_finish / settle_build).
 int radix_launch_passes(const ndt_ctx* c) {
     if (c->rerun_full) return 4;
-    return c->radix_force > 0 ? std::min(c->radix_force, 4) : c->radix_pred;
+    return c->opt.radix_force > 0 ? std::min(c->opt.radix_force, 4) : c->radix_pred;
 }
 void note_grid_width(ndt_ctx* c, long long cells, int dense) {
     if (cells <= 0) return;
@@ -93,7 +93,7 @@ ndt_status enqueue_bin_and_sort(ndt_ctx* c, Lane L, const float4* pts, int n, in
     TRY(ensure(c, L.s.seg_start, (size_t)n + 1));
     // min/max partials (and the digit histograms cleared), then keys: every keys workgroup derives the header itself
     hipLaunchKernelGGL(k_minmax, dim3(nb_mm), dim3(kBlock), 0, L.st, pts, n, dense, L.s.mm.p, L.s.radix_aux.p,
-                       cloud_span ? c->d_clk + 3 : nullptr, nullptr, nullptr, nullptr);
+                       cloud_span ? c->d_clk.p + 3 : nullptr, nullptr, nullptr, nullptr);
     const int nb_keys = std::max(1, std::min(ceil_div(n, 4 * kBlock), 512));
     hipLaunchKernelGGL(k_keys, dim3(nb_keys), dim3(kBlock), 0, L.st, pts, n, dense, L.s.mm.p, nb_mm, h, leaf, c->prm.min_points_per_voxel,
                        c->prm.min_covar_eigvalue_mult, layout, binning, L.s.k0.p, L.s.v0.p, L.s.radix_aux.p, L.s.radix_status.p,

@@ -40,8 +40,8 @@ ndt_status prepare_target_buffers(ndt_ctx* c, int M, int* nb_cloud) {
 ndt_status launch_finalize(ndt_ctx* c, int M, int nb_cloud) {
     // three waves per SIMD below ~4 M target points (C2 / C3 localmaps), two above (C5: the larger register file wins)
     auto* fin = M < kFinalize3WavesMaxPoints ? k_leaf_finalize<3> : k_leaf_finalize<2>;
-    hipLaunchKernelGGL(fin, dim3(nb_cloud), dim3(kBlock), 0, c->stream, c->target_ptr, c->s.k0.p, c->s.k1.p, c->s.v0.p,
-                       c->s.v1.p, c->s.cloud_span.p, c->d_hdr, c->recs.p, c->cent.p, c->icovd.p, c->cloud_key.p,
+    hipLaunchKernelGGL(fin, dim3(nb_cloud), dim3(kBlock), 0, c->stream.get(), c->target_ptr, c->s.k0.p, c->s.k1.p, c->s.v0.p,
+                       c->s.v1.p, c->s.cloud_span.p, c->d_hdr.p, c->recs.p, c->cent.p, c->icovd.p, c->cloud_key.p,
                        c->evals.p, c->grid.p, c->table.p, c->valid_part.p);
     HIPCHK(c, hipGetLastError());
     return NDT_OK;
@@ -56,7 +56,7 @@ ndt_status enqueue_target_build(ndt_ctx* c) {
     // precision_mode 2 (ndt_cpu) bins like cpu::VoxelGrid (division), the others like pclomp's VGC (multiplication)
     // keys, sort, segments and the cloud voxels (>= min points) in key order; then the lookup structure chosen and
     // cleared, then the finalize
-    TRY(enqueue_bin_and_sort(c, main_lane(c), c->target_ptr, M, c->target_dense, c->d_hdr, c->prm.resolution, 0, c->prm.precision_mode == 2 ? 1 : 0,
+    TRY(enqueue_bin_and_sort(c, main_lane(c), c->target_ptr, M, c->target_dense, c->d_hdr.p, c->prm.resolution, 0, c->prm.precision_mode == 2 ? 1 : 0,
                              c->s.cloud_span.p, radix_launch_passes(c)));
     TRY(launch_finalize(c, M, nb_cloud));
     // a pclomp grid over a dense cloud can be extended by merge (its sorted keys / indices stay in c->s)
@@ -72,7 +72,7 @@ ndt_status enqueue_target_append(ndt_ctx* c, int n_old, int n_new, const float4*
     const int M = n_old + n_new;
     int nb_cloud = 0;
     TRY(prepare_target_buffers(c, M, &nb_cloud));
-    Lane Q{c->stream, c->s_inc};
+    Lane Q{c->stream.get(), c->s_inc};
     // new_src: the new points are read there and stored after the old ones by k_minmax (no separate copy launch)
     float4* copy_to = new_src ? const_cast<float4*>(c->target_ptr) + n_old : nullptr;
     const float4* pts_new = new_src ? new_src : c->target_ptr + n_old;
@@ -85,31 +85,31 @@ ndt_status enqueue_target_append(ndt_ctx* c, int n_old, int n_new, const float4*
     TRY(ensure(c, Q.s.radix_aux, kRadixAuxWords));
     TRY(ensure(c, Q.s.radix_status, radix_status_words(nb_sort)));
     TRY(ensure(c, c->s.seg_start, (size_t)M + 1));
-    hipLaunchKernelGGL(k_minmax, dim3(nb_mm), dim3(kBlock), 0, c->stream, pts_new, n_new, 1, Q.s.mm.p, Q.s.radix_aux.p, c->d_clk + 3,
-                       c->d_hdr, c->d_hdr_prev, copy_to);
+    hipLaunchKernelGGL(k_minmax, dim3(nb_mm), dim3(kBlock), 0, c->stream.get(), pts_new, n_new, 1, Q.s.mm.p, Q.s.radix_aux.p, c->d_clk.p + 3,
+                       c->d_hdr.p, c->d_hdr_prev.p, copy_to);
     // the target's points are all in place now: getFitnessScore's index (fit lane) may start beside the rest
-    if (c->tgt_ev_valid) HIPCHK(c, hipEventRecord(c->ev_tgt, c->stream));
+    if (c->tgt_ev_valid) HIPCHK(c, hipEventRecord(c->ev_tgt.get(), c->stream.get()));
     // k_keys also clears the grown target's lookup structure (its whole dense grid or hash table): sized for that as well
     // as for the new points, capped as in a full build
     const long long clear_words = std::max<long long>((long long)c->grid.cap, 2LL << c->max_log2cap) / 4;
     const int nb_keys = std::max(1, (int)std::min<long long>(std::max<long long>(ceil_div(nq, 4 * kBlock), ceil_div(clear_words, 4LL * kBlock)), 512));
-    hipLaunchKernelGGL(k_keys, dim3(nb_keys), dim3(kBlock), 0, c->stream, pts_new, n_new, 1, Q.s.mm.p, nb_mm, c->d_hdr, c->prm.resolution,
+    hipLaunchKernelGGL(k_keys, dim3(nb_keys), dim3(kBlock), 0, c->stream.get(), pts_new, n_new, 1, Q.s.mm.p, nb_mm, c->d_hdr.p, c->prm.resolution,
                        c->prm.min_points_per_voxel, c->prm.min_covar_eigvalue_mult, 0, 0, Q.s.k0.p, Q.s.v0.p, Q.s.radix_aux.p,
                        Q.s.radix_status.p, (int)radix_status_words(nb_sort), c->grid.p, (long long)c->grid.cap, c->table.p, 1LL << c->max_log2cap,
-                       c->d_hdr_prev, n_old);
+                       c->d_hdr_prev.p, n_old);
     const int passes = radix_launch_passes(c);
     for (int pass = 0; pass < passes; ++pass)
-        launch_radix_pass(c, Q, items, nb_sort, Q.s.k0.p, Q.s.v0.p, Q.s.k1.p, Q.s.v1.p, n_new, pass, c->d_hdr, c->d_hdr, passes - 1);
-    hipLaunchKernelGGL(k_merge_append, dim3(std::max(1, ceil_div(M, kMergeTileKeys))), dim3(kBlock), 0, c->stream, c->s.k0.p, c->s.v0.p,
-                       c->s.k1.p, c->s.v1.p, c->d_hdr_prev, n_old, Q.s.k0.p, Q.s.v0.p, Q.s.k1.p, Q.s.v1.p, n_new, c->d_hdr,
+        launch_radix_pass(c, Q, items, nb_sort, Q.s.k0.p, Q.s.v0.p, Q.s.k1.p, Q.s.v1.p, n_new, pass, c->d_hdr.p, c->d_hdr.p, passes - 1);
+    hipLaunchKernelGGL(k_merge_append, dim3(std::max(1, ceil_div(M, kMergeTileKeys))), dim3(kBlock), 0, c->stream.get(), c->s.k0.p, c->s.v0.p,
+                       c->s.k1.p, c->s.v1.p, c->d_hdr_prev.p, n_old, Q.s.k0.p, Q.s.v0.p, Q.s.k1.p, Q.s.v1.p, n_new, c->d_hdr.p,
                        c->target_ptr);
     const Lane L = main_lane(c);
     const int nb_seg = std::max(1, ceil_div(M, kTileKeys));
     ScanCtx sc, sc2;
     TRY(scan_ctx(c, L, nb_seg, &sc));
-    hipLaunchKernelGGL(k_seg_scan, dim3(nb_seg), dim3(kBlock), 0, c->stream, c->s.k0.p, c->s.k1.p, M, c->d_hdr, c->s.seg_start.p, sc);
+    hipLaunchKernelGGL(k_seg_scan, dim3(nb_seg), dim3(kBlock), 0, c->stream.get(), c->s.k0.p, c->s.k1.p, M, c->d_hdr.p, c->s.seg_start.p, sc);
     TRY(scan_ctx(c, L, nb_seg, &sc2));
-    hipLaunchKernelGGL(k_cloud_scan, dim3(nb_seg), dim3(kBlock), 0, c->stream, c->s.seg_start.p, M, c->d_hdr, c->s.cloud_span.p, sc2,
+    hipLaunchKernelGGL(k_cloud_scan, dim3(nb_seg), dim3(kBlock), 0, c->stream.get(), c->s.seg_start.p, M, c->d_hdr.p, c->s.cloud_span.p, sc2,
                        c->max_log2cap);
     TRY(launch_finalize(c, M, nb_cloud));
     return NDT_OK;
@@ -123,8 +123,8 @@ ndt_status enqueue_target_append(ndt_ctx* c, int n_old, int n_new, const float4*
 ndt_status build_target(ndt_ctx* c) {
     ++c->tgt_gen;
     // the target's points are in place: getFitnessScore's index (fit lane) may start beside the build
-    c->tgt_ev_valid = c->fit_tgt_used;
-    if (c->tgt_ev_valid) HIPCHK(c, hipEventRecord(c->ev_tgt, c->stream));
+    c->tgt_ev_valid = c->lanes.fit_tgt_used;
+    if (c->tgt_ev_valid) HIPCHK(c, hipEventRecord(c->ev_tgt.get(), c->stream.get()));
     TRY(enqueue_target_build(c));
     c->build_unchecked = true;
     c->built_since_align = true;
@@ -143,7 +143,7 @@ ndt_status build_target(ndt_ctx* c) {
 ndt_status rerun_build(ndt_ctx* c, int berr) {
     ++c->n_builds_rerun;
     if (berr & kBuildErrLookback) {
-        c->tile_tickets = true;
+        c->opt.tile_tickets = true;
         ++c->n_rerun_lookback;
     }
     c->inc_ok = false;
@@ -158,8 +158,8 @@ ndt_status rerun_build(ndt_ctx* c, int berr) {
 ndt_status settle_build(ndt_ctx* c) {
     if (!c->build_unchecked || !c->grid_valid) return NDT_OK;
     for (int attempt = 0;; ++attempt) {
-        HIPCHK(c, hipMemcpyAsync(c->h_hdr, c->d_hdr, sizeof(GridHeader), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_hdr.get(), c->d_hdr.p, sizeof(GridHeader), hipMemcpyDeviceToHost, c->stream.get()));
+        HIPCHK(c, hipStreamSynchronize(c->stream.get()));
         const int berr = c->h_hdr->pad[0];
         if (!berr) break;
         if (attempt > 0) return fail(c, NDT_EDEVICE, "target build failed twice (error bits " + std::to_string(berr) + ")");
@@ -178,8 +178,8 @@ ndt_status upload_points(ndt_ctx* c, DevBuf<float4>& dst, const float* xyz, size
         const float* f = reinterpret_cast<const float*>(base + i * stride_bytes);
         tmp[i] = make_float4(f[0], f[1], f[2], 1.0f);
     }
-    if (n) HIPCHK(c, hipMemcpyAsync(dst.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n) HIPCHK(c, hipMemcpyAsync(dst.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     return NDT_OK;
 }
 
@@ -200,13 +200,13 @@ static ndt_status append_target(ndt_ctx* c, const float4* d_new, const float* h_
         // a larger owned buffer (or the first owned copy of a caller-referenced target), old points first
         DevBuf<float4> nb;
         TRY(ensure(c, nb, std::max(m, m0 + m0 / 2)));
-        if (m0) HIPCHK(c, hipMemcpyAsync(nb.p, c->target_ptr, m0 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (m0) HIPCHK(c, hipMemcpyAsync(nb.p, c->target_ptr, m0 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream.get()));
+        HIPCHK(c, hipStreamSynchronize(c->stream.get()));
         std::swap(c->target.p, nb.p);  // nb frees the previous copy
         std::swap(c->target.cap, nb.cap);
     }
     if (d_new) {
-        HIPCHK(c, hipMemcpyAsync(c->target.p + m0, d_new, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->target.p + m0, d_new, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream.get()));
     } else {
         std::vector<float4> tmp(n);
         const char* base = reinterpret_cast<const char*>(h_new);
@@ -214,8 +214,8 @@ static ndt_status append_target(ndt_ctx* c, const float4* d_new, const float* h_
             const float* f = reinterpret_cast<const float*>(base + i * stride_bytes);
             tmp[i] = make_float4(f[0], f[1], f[2], 1.0f);
         }
-        HIPCHK(c, hipMemcpyAsync(c->target.p + m0, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->target.p + m0, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream.get()));
+        HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     }
     c->target_ptr = c->target.p;
     c->M = (int)m;
@@ -277,8 +277,8 @@ ndt_status ndt_set_target_append_device(ndt_ctx* c, float* d_xyz4, size_t n_old,
         return build_target(c);
     }
     ++c->tgt_gen;
-    c->tgt_ev_valid = c->fit_tgt_used;
-    if (c->tgt_ev_valid && !new_src) HIPCHK(c, hipEventRecord(c->ev_tgt, c->stream));
+    c->tgt_ev_valid = c->lanes.fit_tgt_used;
+    if (c->tgt_ev_valid && !new_src) HIPCHK(c, hipEventRecord(c->ev_tgt.get(), c->stream.get()));
     const ndt_status st = enqueue_target_append(c, (int)n_old, (int)n_new, new_src);
     if (st != NDT_OK) {
         c->inc_ok = false;
@@ -310,8 +310,8 @@ ndt_status ndt_grid_info(ndt_ctx* c, int header[16]) {
     TRY(set_dev(c));
     if (!c->grid_valid) TRY(build_target(c));
     TRY(settle_build(c));
-    HIPCHK(c, hipMemcpyAsync(c->h_hdr, c->d_hdr, sizeof(GridHeader), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_hdr.get(), c->d_hdr.p, sizeof(GridHeader), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     const GridHeader& h = *c->h_hdr;
     c->grid_cells_seen = std::max(c->grid_cells_seen, h.cells);
     for (int a = 0; a < 3; ++a) { header[a] = h.min_b[a]; header[3 + a] = h.max_b[a]; header[6 + a] = h.div_b[a]; header[9 + a] = h.divb_mul[a]; }

@@ -13,6 +13,25 @@ static bool valid_params(const ndt_params* p) {
            p->min_points_per_voxel >= 1 && p->precision_mode >= 0 && p->precision_mode <= 2;
 }
 
+// what every ctx holds from its creation on: the fixed-size device objects, their pinned counterparts, the target marker
+static ndt_status create_buffers(ndt_ctx* c) {
+    for (DevBuf<GridHeader>* h : {&c->d_hdr, &c->d_hdr_ds, &c->d_hdr_prev, &c->fe.d_hdr, &c->fit_ix.hdr, &c->fe.sor_ix.hdr}) TRY(ensure(c, *h, 1));
+    HIPCHK(c, hipMemset(c->fe.d_hdr.p, 0, sizeof(GridHeader)));
+    TRY(make_pinned(c, c->h_hdr, 1, hipHostMallocDefault));
+    TRY(ensure(c, c->d_state, 1));
+    TRY(ensure(c, c->d_state2, 1));
+    TRY(make_pinned(c, c->h_state, 1, hipHostMallocCoherent));
+    TRY(make_pinned(c, c->h_rb, 8, hipHostMallocCoherent));
+    TRY(ensure(c, c->d_clk, 4));
+    TRY(ensure(c, c->d_hist, c->hist_cap));
+    TRY(ensure(c, c->d_async, 1));
+    TRY(make_pinned(c, c->h_async, 1, hipHostMallocDefault));
+    TRY(make_event(c, c->ev_tgt, hipEventDisableTiming));
+    std::memset(c->h_state.get(), 0, sizeof(AlignState));
+    std::memset(c->h_rb.get(), 0, 8 * sizeof(unsigned long long));
+    return NDT_OK;
+}
+
 extern "C" {
 
 ndt_status ndt_default_params(ndt_params* out) {
@@ -46,63 +65,18 @@ ndt_status ndt_create(const ndt_params* params, ndt_ctx** out) {
     // (getFitnessScore, keyframe insertion) at the lowest
     int prio_least = 0, prio_greatest = 0;
     if (hipSetDevice(c->device) != hipSuccess || hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess ||
-        hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_greatest) != hipSuccess) {
+        make_stream(c, c->stream, prio_greatest) != NDT_OK) {
         delete c;
         return NDT_EDEVICE;
     }
     int n_cu = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && n_cu > 0) c->n_cu = n_cu;
-    // A/B: NDT_LANE_CUS = k side-lane CUs (NDT_LANE_CU_MODE 0: every (n_cu / k)-th CU, 1: the first k), the main stream
-    // on the rest (its pass grids sized for them)
-    if (const char* e = std::getenv("NDT_LANE_CUS")) {
-        const int k = std::atoi(e);
-        const int mode = std::getenv("NDT_LANE_CU_MODE") ? std::atoi(std::getenv("NDT_LANE_CU_MODE")) : 0;
-        if (k > 0 && k < c->n_cu) {
-            const int words = (c->n_cu + 31) / 32, stride = c->n_cu / k;
-            std::vector<uint32_t> main_mask(words, 0u);
-            c->lane_mask.assign(words, 0u);
-            int taken = 0;
-            for (int i = 0; i < c->n_cu; ++i) {
-                const bool lane = mode == 1 ? i < k : (i % stride == stride - 1 && taken < k);
-                if (lane) ++taken;
-                (lane ? c->lane_mask : main_mask)[i / 32] |= 1u << (i % 32);
-            }
-            hipStream_t ms = nullptr;
-            if (hipExtStreamCreateWithCUMask(&ms, (uint32_t)words * 32, main_mask.data()) == hipSuccess) {
-                (void)hipStreamDestroy(c->stream);
-                c->stream = ms;
-                c->n_cu -= taken;
-            } else {
-                c->lane_mask.clear();
-            }
-        }
-    }
-    if (const char* e = std::getenv("NDT_PPT")) c->opt_ppt = std::max(1, std::min(3, std::atoi(e)));  // A/B runs (pass geometry)
+    if (const char* e = std::getenv("NDT_PPT")) c->opt.ppt = std::max(1, std::min(3, std::atoi(e)));  // A/B runs (pass geometry)
     gauss_constants(0.55, 1.0f, &c->gauss_cur[0], &c->gauss_cur[1], &c->gauss_cur[2]);
-    bool ok = hipMalloc(&c->d_hdr, sizeof(GridHeader)) == hipSuccess && hipMalloc(&c->d_hdr_ds, sizeof(GridHeader)) == hipSuccess &&
-              hipMalloc(&c->d_hdr_prev, sizeof(GridHeader)) == hipSuccess &&
-              hipMalloc(&c->d_hdr_fe, sizeof(GridHeader)) == hipSuccess && hipMemset(c->d_hdr_fe, 0, sizeof(GridHeader)) == hipSuccess &&
-              hipMalloc(&c->fit_ix.hdr, sizeof(GridHeader)) == hipSuccess &&
-              hipMalloc(&c->sor_ix.hdr, sizeof(GridHeader)) == hipSuccess &&
-              hipHostMalloc(&c->h_hdr, sizeof(GridHeader), hipHostMallocDefault) == hipSuccess &&
-
-              hipMalloc(&c->d_state, sizeof(AlignState)) == hipSuccess && hipMalloc(&c->d_state2, sizeof(AlignState)) == hipSuccess &&
-              hipHostMalloc(&c->h_state, sizeof(AlignState), hipHostMallocCoherent) == hipSuccess &&
-              hipHostMalloc(&c->h_rb, 8 * sizeof(unsigned long long), hipHostMallocCoherent) == hipSuccess &&
-              hipMalloc(&c->d_clk, 4 * sizeof(unsigned long long)) == hipSuccess &&
-              hipMalloc(&c->d_hist, sizeof(PassRecordDev) * c->hist_cap) == hipSuccess &&
-
-              hipMalloc(&c->d_async, sizeof(ndt_ctx::AsyncOut)) == hipSuccess &&
-              hipHostMalloc(&c->h_async, sizeof(ndt_ctx::AsyncOut), hipHostMallocDefault) == hipSuccess &&
-              hipEventCreateWithFlags(&c->ev_fit, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&c->ev_ins, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&c->ev_tgt, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
+    if (create_buffers(c) != NDT_OK) {
         ndt_destroy(c);
         return NDT_ENOMEM;
     }
-    std::memset(c->h_state, 0, sizeof(AlignState));
-    std::memset(c->h_rb, 0, 8 * sizeof(unsigned long long));
     *out = c;
     return NDT_OK;
 }
@@ -129,7 +103,7 @@ ndt_status ndt_set_params(ndt_ctx* c, const ndt_params* p) {
 ndt_status ndt_memcpy_d2d(ndt_ctx* c, void* d_dst, const void* d_src, size_t bytes) {
     if (!c || (bytes && (!d_dst || !d_src))) return fail(c, NDT_EINVAL, "null argument");
     TRY(set_dev(c));
-    if (bytes) TRY(copy16(c, c->stream, d_dst, d_src, bytes));
+    if (bytes) TRY(copy16(c, c->stream.get(), d_dst, d_src, bytes));
     return NDT_OK;
 }
 
@@ -166,10 +140,10 @@ ndt_status ndt_synchronize(ndt_ctx* c) {
     TRY(set_dev(c));
     TRY(flush_source(c));  // after a synchronize the caller may reuse the buffer it set as source
     // the side lanes' host threads first (every posted job issued; a job's failure stays for its result call)
-    for (LaneWorker* w : {c->fit_worker, c->ins_worker}) if (w) (void)w->drain(nullptr);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->fit_stream) HIPCHK(c, hipStreamSynchronize(c->fit_stream));
-    if (c->ins_stream) HIPCHK(c, hipStreamSynchronize(c->ins_stream));
+    for (LaneWorker* w : {c->lanes.fit_worker.get(), c->lanes.ins_worker.get()}) if (w) (void)w->drain(nullptr);
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
+    if (c->lanes.fit_stream) HIPCHK(c, hipStreamSynchronize(c->lanes.fit_stream.get()));
+    if (c->lanes.ins_stream) HIPCHK(c, hipStreamSynchronize(c->lanes.ins_stream.get()));
     return NDT_OK;
 }
 
@@ -178,12 +152,12 @@ ndt_status ndt_last_timings(ndt_ctx* c, double* ms_build, double* ms_align, doub
     if (ms_build) *ms_build = c->ms_build;
     if (ms_align) *ms_align = c->ms_align;
     // pass statistics over this ctx and the helper contexts of ndt_align_batch (the batch's other streams)
-    double ms = c->prof_ms_sum, bytes = c->prof_bytes_sum;
-    long long cnt = c->prof_count;
+    double ms = c->prof.stats.ms_sum, bytes = c->prof.stats.bytes_sum;
+    long long cnt = c->prof.stats.count;
     for (const ndt_ctx* h : c->helpers) {
-        ms += h->prof_ms_sum;
-        bytes += h->prof_bytes_sum;
-        cnt += h->prof_count;
+        ms += h->prof.stats.ms_sum;
+        bytes += h->prof.stats.bytes_sum;
+        cnt += h->prof.stats.count;
     }
     if (ms_pass_avg) *ms_pass_avg = cnt ? ms / cnt : 0.0;
     if (pass_bytes_avg) *pass_bytes_avg = cnt ? bytes / cnt : 0.0;
@@ -192,9 +166,10 @@ ndt_status ndt_last_timings(ndt_ctx* c, double* ms_build, double* ms_align, doub
 
 ndt_status ndt_pass_phases(ndt_ctx* c, double ms[22]) {
     if (!c || !ms) return NDT_EINVAL;
-    for (int q = 0; q < 7; ++q) ms[q] = c->prof_phase_count ? c->prof_phase_sum[q] / c->prof_phase_count : 0.0;
-    for (int q = 0; q < 5; ++q) ms[7 + q] = c->prof_body_count ? c->prof_body_sum[q] / c->prof_body_count : 0.0;
-    for (int q = 0; q < 10; ++q) ms[12 + q] = c->prof_tail_count ? c->prof_tail_sum[q] / c->prof_tail_count : 0.0;
+    const PassProf::Stats& ps = c->prof.stats;
+    for (int q = 0; q < 7; ++q) ms[q] = ps.phase_count ? ps.phase_sum[q] / ps.phase_count : 0.0;
+    for (int q = 0; q < 5; ++q) ms[7 + q] = ps.body_count ? ps.body_sum[q] / ps.body_count : 0.0;
+    for (int q = 0; q < 10; ++q) ms[12 + q] = ps.tail_count ? ps.tail_sum[q] / ps.tail_count : 0.0;
     return NDT_OK;
 }
 
@@ -203,19 +178,19 @@ ndt_status ndt_set_pass_options(ndt_ctx* c, int lead_tail, int points_per_thread
         source_order > 1)
         return fail(c, NDT_EINVAL, "bad pass options");
     if (c->al_inflight) return fail(c, NDT_EINVAL, "an asynchronous align is in flight (ndt_align_wait first)");
-    c->opt_lead_tail = lead_tail != 0;
-    c->opt_ppt = points_per_thread;
-    c->order_source = source_order != 0;
-    for (ndt_ctx* h : c->helpers) TRY(ndt_set_pass_options(h, lead_tail, points_per_thread, source_order));
+    c->opt.lead_tail = lead_tail != 0;
+    c->opt.ppt = points_per_thread;
+    c->opt.order_source = source_order != 0;
+    for (ndt_ctx* h : c->helpers) hand_options(h, c);
     return NDT_OK;
 }
 
 ndt_status ndt_set_build_options(ndt_ctx* c, int tile_tickets, int radix_passes) {
     if (!c || tile_tickets < 0 || tile_tickets > 1 || radix_passes < 0 || radix_passes > 4) return fail(c, NDT_EINVAL, "bad build options");
     if (c->al_inflight) return fail(c, NDT_EINVAL, "an asynchronous align is in flight (ndt_align_wait first)");
-    c->tile_tickets = tile_tickets != 0;
-    c->radix_force = radix_passes;
-    for (ndt_ctx* h : c->helpers) TRY(ndt_set_build_options(h, tile_tickets, radix_passes));
+    c->opt.tile_tickets = tile_tickets != 0;
+    c->opt.radix_force = radix_passes;
+    for (ndt_ctx* h : c->helpers) h->opt = c->opt;  // tile_tickets = 0 clears a helper's sticky flag too
     return NDT_OK;
 }
 
@@ -225,14 +200,14 @@ ndt_status ndt_build_stats(ndt_ctx* c, long long out[6]) {
     out[1] = c->n_builds_merge;
     out[2] = c->n_builds_rerun;
     out[3] = c->n_rerun_lookback;
-    out[4] = c->tile_tickets ? 1 : 0;
+    out[4] = c->opt.tile_tickets ? 1 : 0;
     out[5] = radix_launch_passes(c);
     for (const ndt_ctx* h : c->helpers) {  // ndt_align_batch's helper contexts (their own streams and builds)
         out[0] += h->n_builds_full;
         out[1] += h->n_builds_merge;
         out[2] += h->n_builds_rerun;
         out[3] += h->n_rerun_lookback;
-        out[4] += h->tile_tickets ? 1 : 0;
+        out[4] += h->opt.tile_tickets ? 1 : 0;
     }
     return NDT_OK;
 }
@@ -240,14 +215,8 @@ ndt_status ndt_build_stats(ndt_ctx* c, long long out[6]) {
 ndt_status ndt_set_profiling(ndt_ctx* c, int enable) {
     if (!c) return NDT_EINVAL;
     for (ndt_ctx* h : c->helpers) TRY(ndt_set_profiling(h, enable));
-    c->profiling = enable != 0;
-    c->prof_ms_sum = c->prof_bytes_sum = 0;
-    for (double& v : c->prof_phase_sum) v = 0;
-    for (double& v : c->prof_body_sum) v = 0;
-    for (double& v : c->prof_tail_sum) v = 0;
-    c->prof_phase_count = c->prof_body_count = c->prof_tail_count = 0;
-    c->prof_count = 0;
-    c->ms_pass_avg = c->pass_bytes_avg = 0;
+    c->opt.profiling = enable != 0;
+    c->prof.stats = PassProf::Stats{};
     // no graph invalidation: the profiling flag and the stamp buffer are part of every graph's cache key, so a call
     // that only resets the statistics keeps the captured chains
     return NDT_OK;
@@ -257,43 +226,17 @@ const char* ndt_last_error(const ndt_ctx* c) { return c ? c->err.c_str() : "null
 
 int ndt_abi_version(void) { return NDT_HIP_ABI_VERSION; }
 
+// Only what is about order; every resource is released by its owner when the ctx goes (member order: see ndt_ctx)
 void ndt_destroy(ndt_ctx* c) {
     if (!c) return;
     for (ndt_ctx* h : c->helpers) ndt_destroy(h);
     c->helpers.clear();
     (void)hipSetDevice(c->device);
-    delete c->fit_worker;  // joins the side lanes' host threads after their queued jobs
-    delete c->ins_worker;
-    c->fit_worker = c->ins_worker = nullptr;
-    for (hipStream_t st : {c->stream, c->fit_stream, c->ins_stream}) if (st) (void)hipStreamSynchronize(st);
+    c->lanes.fit_worker.reset();  // joins the side lanes' host threads after their queued jobs
+    c->lanes.ins_worker.reset();
+    for (hipStream_t st : {c->stream.get(), c->lanes.fit_stream.get(), c->lanes.ins_stream.get()}) if (st) (void)hipStreamSynchronize(st);
     invalidate_graph(c);
-    // every DevBuf goes with the ctx (delete c, below); what follows is the memory, events and streams held raw
-    for (NNIndex* ix : {&c->fit_ix, &c->sor_ix}) if (ix->hdr) (void)hipFree(ix->hdr);
-    if (c->d_hdr) (void)hipFree(c->d_hdr);
-    if (c->d_hdr_ds) (void)hipFree(c->d_hdr_ds);
-    if (c->d_hdr_prev) (void)hipFree(c->d_hdr_prev);
-    if (c->d_hdr_fe) (void)hipFree(c->d_hdr_fe);
-    if (c->d_hdr_ins) (void)hipFree(c->d_hdr_ins);
-    if (c->h_hdr) (void)hipHostFree(c->h_hdr);
-    if (c->d_async) (void)hipFree(c->d_async);
-    if (c->h_async) (void)hipHostFree(c->h_async);
-    if (c->ev_fit) (void)hipEventDestroy(c->ev_fit);
-    if (c->ev_ins) (void)hipEventDestroy(c->ev_ins);
-    if (c->h_ts) (void)hipHostFree(c->h_ts);
-    if (c->h_hist) (void)hipHostFree(c->h_hist);
-    if (c->d_state) (void)hipFree(c->d_state);
-    if (c->d_state2) (void)hipFree(c->d_state2);
-    if (c->h_state) (void)hipHostFree(c->h_state);
-    if (c->h_rb) (void)hipHostFree(c->h_rb);
-    if (c->d_clk) (void)hipFree(c->d_clk);
-    if (c->d_hist) (void)hipFree(c->d_hist);
-    if (c->icp_graph) (void)hipGraphExecDestroy(c->icp_graph);
-    if (c->d_icp) (void)hipFree(c->d_icp);
-    if (c->h_icp) (void)hipHostFree(c->h_icp);
-    if (c->d_icp_hist) (void)hipFree(c->d_icp_hist);
-    for (auto e : {c->ev_tgt, c->ev_main_fit, c->ev_main_ins, c->ev_fit_src, c->ev_fit_tgt}) if (e) (void)hipEventDestroy(e);
-    for (auto e : c->pass_ev) (void)hipEventDestroy(e);
-    for (hipStream_t st : {c->stream, c->fit_stream, c->ins_stream}) if (st) (void)hipStreamDestroy(st);
+    c->icp.graph.reset();
     delete c;
 }
 

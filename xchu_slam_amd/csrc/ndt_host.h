@@ -13,6 +13,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <shared_mutex>
 #include <thread>
@@ -24,6 +25,8 @@ namespace ndt::host {
 
 constexpr int kTileKeys = kBlock * 16;
 
+// The owners of the host side's GPU resources.  Nothing outside them releases device memory, pinned memory, an event, a
+// stream or a graph exec: an owner's member order in its struct is the release order (reverse of declaration).
 // A device buffer that owns its memory: freed with its owner (the ctx, a lane's scratch, a call's temporaries)
 template <typename T> struct DevBuf {
     T* p = nullptr;
@@ -31,8 +34,23 @@ template <typename T> struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {  // by swap: what this held goes with o
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
+
+struct PinnedFree { void operator()(void* p) const { (void)hipHostFree(p); } };
+struct EventDestroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+struct GraphExecDestroy { void operator()(hipGraphExec_t g) const { (void)hipGraphExecDestroy(g); } };
+template <typename T> using Pinned = std::unique_ptr<T, PinnedFree>;  // pinned host memory: Pinned<X> or Pinned<X[]>
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
+using GraphExec = std::unique_ptr<std::remove_pointer_t<hipGraphExec_t>, GraphExecDestroy>;
 
 struct Scratch {
     DevBuf<int> k0, v0, k1, v1, radix_aux, seg_start, flags, cloud_idx;
@@ -107,12 +125,21 @@ struct LaneWorker {
     void run();  // host_lanes.hip
 };
 
+// A descriptor database's per-slot arrays (Scan Context, Intensity Scan Context), carved from one device block:
+// arr[k] holds cap slots of the k-th array (reserve_slots)
+struct SlotArrays {
+    DevBuf<char> block;
+    size_t cap = 0;  // slots allocated
+    std::vector<char*> arr;
+    template <typename T> T* at(int k) const { return reinterpret_cast<T*>(arr[k]); }
+};
+
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Exact nearest-neighbour index over a cloud (block-major binning, layout 1 of k_header): the points sorted into
 // 8x8x8-cell blocks, a block table and per-occupied-block cell offsets.
 struct NNIndex {
-    GridHeader* hdr = nullptr;          // binning (device)
+    DevBuf<GridHeader> hdr;             // binning (device)
     DevBuf<float4> pts;                 // points in (block, cell) order
     DevBuf<int> keys, start;            // per occupied cell: key, first point
     DevBuf<int> blk, off;               // block table + per-occupied-block cell offsets
@@ -124,14 +151,108 @@ struct NNIndex {
 using namespace ndt;
 using namespace ndt::host;
 
+// The members below that only one host unit touches (plus ndt_create / ndt_destroy) are grouped by that unit.
+
+// The caller-set options (ndt_set_pass_options, ndt_set_build_options, ndt_set_profiling) as one struct: the batched
+// replay's helper contexts take them by one assignment (hand_options)
+struct CtxOptions {
+    // pass chains: leading-tail chains where an align is latency-bound, two points per thread in large
+    // last-workgroup-tail passes, the source in target-cell order
+    bool lead_tail = true;
+    int ppt = 2;
+    bool order_source = true;
+    // target build (test hook): radix_force fixes the radix pass count; tile_tickets (sticky once a look-back timed out,
+    // or set by the hook) takes every sort's tiles by atomic ticket
+    int radix_force = 0;
+    bool tile_tickets = false;
+    bool profiling = false;
+};
+
+// host_lanes.hip — the side lanes, created as a whole on the first side-lane call (side_lanes): fit_stream runs
+// getFitnessScore's index build and query, ins_stream the keyframe insertion, each issued by its own host thread.
+// ev_main_* are the main-stream markers a side-lane job waits on; ev_fit_src / ev_fit_tgt mark (fit_stream) the end of
+// the last query that read the ctx's source / of the last index build that read the ctx's target points (main waits
+// on them before it rewrites what the index or query read); ev_fit / ev_ins mark a result in ndt_ctx::h_async.
+// Streams first, workers last: a worker is joined before anything it launches on or into is released.
+struct SideLanes {
+    Stream fit_stream, ins_stream;
+    Event ev_main_fit, ev_main_ins, ev_fit_src, ev_fit_tgt, ev_fit, ev_ins;
+    Scratch s_fit, s_ins;
+    DevBuf<GridHeader> d_hdr_ins;       // keyframe insertion's VoxelGrid binning
+    DevBuf<float4> ins_tr, ins_ds;      // keyframe insertion scratch (transformed scan, VoxelGrid output)
+    size_t ins_n_in = 0;
+    int marked = 0;  // ndt_side_lanes_mark: bit 0 the next fitness query, bit 1 the next insertion use ev_main_fit as is
+    bool fit_pending = false, ins_pending = false;
+    bool fit_src_used = false, fit_tgt_used = false;
+    std::unique_ptr<LaneWorker> fit_worker, ins_worker;  // host threads issuing the side lanes' launches
+};
+
+// host_front_end.hip — filter_node's front end (ndt_filter_scan): scratch + the last call's SOR statistics
+struct FrontEnd {
+    DevBuf<GridHeader> d_hdr;           // the filter's compaction scans: pad[0] look-back timeout flag, pad[1] kept count
+    NNIndex sor_ix;                     // nearest-neighbour index over a filtered scan (StatisticalOutlierRemoval)
+    DevBuf<int> flags, idx;
+    DevBuf<float4> in, crop, ds, out;
+    DevBuf<float> dist;
+    DevBuf<double> thr;
+    size_t nvox = 0;
+};
+
+// host_align.hip (and the two profiling entry points) — pass profiling: the stamp buffer and its pinned copies, which
+// are part of every graph's cache key and stay, and the statistics ndt_set_profiling resets
+struct PassProf {
+    DevBuf<unsigned long long> ts;      // per-pass kTsStride s_memrealtime stamps
+    Pinned<unsigned long long[]> h_ts;  // pinned copies, filled by k_readback before the align's sync (made together)
+    Pinned<PassRecordDev[]> h_hist;
+    struct Stats {
+        double phase_sum[7] = {0, 0, 0, 0, 0, 0, 0};
+        int phase_count = 0;
+        double body_sum[5] = {0, 0, 0, 0, 0};
+        int body_count = 0;
+        double tail_sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        int tail_count = 0;
+        double ms_sum = 0, bytes_sum = 0;
+        long long count = 0;
+    } stats;
+};
+
+// host_icp.hip — point-to-point ICP (ndt_icp_align): the cumulative cloud X, per-point match / d2 of the last pass, the
+// pass partials and ticket, the device state and history with the pinned state copies ([0] read back, [1] the initial
+// state; the three made together), and the last run's result.  The graph exec last: released before the buffers it names.
+struct IcpRun {
+    DevBuf<float4> x;
+    DevBuf<int> match;
+    DevBuf<float> d2;
+    DevBuf<double> part;
+    DevBuf<unsigned> ticket;
+    DevBuf<IcpState> d_state;
+    DevBuf<IcpRecordDev> d_hist;
+    Pinned<IcpState[]> h_state;
+    bool used = false;                  // the fit index of this ctx carries the points' original indices from now on
+    bool last = false;                  // the result have_result speaks of is the ICP's (final_tf), not the NDT align's
+    float final_tf[16] = {0};
+    int n = 0;                          // source points of the last ICP align
+    std::vector<IcpRecordDev> hist;
+    GraphExec graph;
+    long long graph_key[12] = {0};
+};
+
+// Member order is part of the design: members are released in reverse order of declaration (delete c, the last step of
+// ndt_destroy, after it has joined the lane workers, synchronised the three streams and dropped the graph execs).  So
+// the main stream is declared before everything that is queued or released on it, capture_mu before the lane workers
+// that hold its address, and the graph execs (icp.graph, graphs) after the buffers their nodes name.
 struct ndt_ctx {
     ndt_params prm{};
     int device = 0;
     int n_cu = 256;  // compute units the main stream's passes spread over (direct-pass grid)
-    // CU partition (NDT_LANE_CUS, A/B): the side lanes run on lane_mask's CUs, the main stream on the others
-    std::vector<uint32_t> lane_mask;
-    hipStream_t stream = nullptr;
+    Stream stream;
     std::string err;
+    CtxOptions opt;
+    // held exclusively while the main stream captures an align graph and shared while a lane thread runs a job: a stream
+    // wait issued by a lane thread during the capture is rejected by the runtime ("dependency created on uncaptured
+    // work"), and the lanes' allocations (hipMalloc / hipFree on growth) stay out of it too; the two lanes issue side by
+    // side
+    std::shared_mutex capture_mu;
     // target grid
     DevBuf<float4> target;            // owned copy for host-provided targets
     const float4* target_ptr = nullptr;  // points the build reads (owned copy or the caller's device buffer)
@@ -140,63 +261,39 @@ struct ndt_ctx {
     bool has_target = false;
     bool grid_valid = false;
     float grid_res = 0.f;
-    GridHeader* d_hdr = nullptr;
-    GridHeader* d_hdr_ds = nullptr;
-    GridHeader* d_hdr_fe = nullptr;  // the filter's compaction scans: pad[0] look-back timeout flag, pad[1] kept count
-    NNIndex fit_ix;                     // nearest-neighbour index over the target (getFitnessScore)
-    NNIndex sor_ix;                     // nearest-neighbour index over a filtered scan (StatisticalOutlierRemoval)
+    DevBuf<GridHeader> d_hdr, d_hdr_ds;
+    Pinned<GridHeader> h_hdr;
+    NNIndex fit_ix;                     // nearest-neighbour index over the target (getFitnessScore, ICP)
     DevBuf<int> fit_cnt;
     DevBuf<unsigned> fit_ticket;        // last-workgroup ticket of k_fitness (re-armed by that workgroup)
-    // asynchronous getFitnessScore / keyframe insertion: results land in pinned memory, an event marks them
+    DevBuf<double> fit_sum;
+    DevBuf<float> fit_d2;
+    int fit_n = 0;                      // source points of the last query
+    bool fit_valid = false;             // index matches the current target
+    // ev_tgt marks (main stream) the current target's points in place — recorded ahead of each build once the fit lane is
+    // in use (tgt_ev_valid); the index build waits on it, not on the voxel build
+    Event ev_tgt;
+    bool tgt_ev_valid = false;
+    // asynchronous getFitnessScore / keyframe insertion / scan filter: results land in pinned memory, an event marks them
     struct AsyncOut {
         double fit_sum;
         long long fit_cnt;
         GridHeader ins_hdr;
         int fe_words[4];  // ndt_filter_scan_device: [0] scan flag, [1] scan count, [2] outlier index sort flag
     };
-    AsyncOut* d_async = nullptr;
-    AsyncOut* h_async = nullptr;        // pinned
-    hipEvent_t ev_fit = nullptr, ev_ins = nullptr;
-    bool fit_pending = false, ins_pending = false;
-    // side lanes (created on first use): fit_stream runs getFitnessScore's index build and query, ins_stream the
-    // keyframe insertion, each issued by its own host thread.  ev_tgt marks (main stream) the current target's points in
-    // place — recorded ahead of each build, the index build waits on it, not on the voxel build; ev_main_* are the
-    // main-stream markers a side-lane job waits on; ev_fit_src / ev_fit_tgt mark (fit_stream) the end of the last query
-    // that read the ctx's source / of the last index build that read the ctx's target points (main waits on them
-    // before it rewrites what the index or query read)
-    hipStream_t fit_stream = nullptr, ins_stream = nullptr;
-    LaneWorker* fit_worker = nullptr;   // host threads issuing the side lanes' launches
-    LaneWorker* ins_worker = nullptr;
-    Scratch s_fit, s_ins;
-    GridHeader* d_hdr_ins = nullptr;    // keyframe insertion's VoxelGrid binning
-    hipEvent_t ev_tgt = nullptr, ev_main_fit = nullptr, ev_main_ins = nullptr, ev_fit_src = nullptr, ev_fit_tgt = nullptr;
-    int lanes_marked = 0;  // ndt_side_lanes_mark: bit 0 the next fitness query, bit 1 the next insertion use ev_main_fit as is
-    bool fit_src_used = false, fit_tgt_used = false;
-    // held exclusively while the main stream captures an align graph and shared while a lane thread runs a job: a stream
-    // wait issued by a lane thread during the capture is rejected by the runtime ("dependency created on uncaptured
-    // work"), and the lanes' allocations (hipMalloc / hipFree on growth) stay out of it too; the two lanes issue side by
-    // side
-    std::shared_mutex capture_mu;
-    int fit_n = 0;                      // source points of the last query
-    size_t ins_n_in = 0;
-    DevBuf<float4> ins_tr, ins_ds;      // keyframe insertion scratch (transformed scan, VoxelGrid output)
-    DevBuf<double> fit_sum;
-    DevBuf<float> fit_d2;
-    bool fit_valid = false;             // index matches the current target
-    GridHeader* h_hdr = nullptr;  // pinned
-    bool tgt_ev_valid = false;  // ev_tgt marks the current target (recorded by build_target once the fit lane is in use)
+    DevBuf<AsyncOut> d_async;
+    Pinned<AsyncOut> h_async;
+    SideLanes lanes;
     Scratch s;
     // merge-extended targets (ndt_set_target_append_device): the new points' sort scratch, the previous header, and whether
     // s's sorted keys / indices and d_hdr still describe the current target (no other main-stream sort since its build)
     Scratch s_inc;
-    GridHeader* d_hdr_prev = nullptr;
+    DevBuf<GridHeader> d_hdr_prev;
     bool inc_ok = false;
     // target-build robustness (GridHeader::pad[0] bits, checked by the align read-back or settle_build): radix passes
-    // launched = the key width of the last grid read back, +1 bit of margin (radix_pred; 4 until a grid was seen);
-    // radix_force (ndt_set_build_options test hook) fixes the count; tile_tickets (sticky once a look-back timed out, or
-    // set by the hook) takes every sort's tiles by atomic ticket; counters for ndt_build_stats
-    int radix_pred = 4, radix_force = 0;
-    bool tile_tickets = false;
+    // launched = the key width of the last grid read back, +1 bit of margin (radix_pred; 4 until a grid was seen, or
+    // what opt.radix_force fixes); counters for ndt_build_stats
+    int radix_pred = 4;
     bool build_unchecked = false;   // a target build queued whose error bits no align / settle_build has read yet
     bool rerun_full = false;        // a re-run build: all four radix passes whatever the prediction or the hook says
     float al_guess[16] = {0};       // the guess of the align in flight (re-run after a flagged build)
@@ -223,29 +320,19 @@ struct ndt_ctx {
     DevBuf<float4> source_ord;
     DevBuf<int> ord_k0, ord_v0, ord_k1, ord_v1;
     const float4* pass_src = nullptr;
-    bool order_source = true;
-    // pass-chain options (ndt_set_pass_options): leading-tail chains where an align is latency-bound, two points per
-    // thread in large last-workgroup-tail passes
-    bool opt_lead_tail = true;
-    int opt_ppt = 2;
-    // filter_node front end (ndt_filter_scan): scratch + the last call's SOR statistics
-    DevBuf<int> fe_flags, fe_idx;
-    DevBuf<float4> fe_in, fe_crop, fe_ds, fe_out;
-    DevBuf<float> fe_dist;
-    DevBuf<double> fe_thr;
-    size_t fe_nvox = 0;
+    FrontEnd fe;
     // align
-    AlignState* d_state = nullptr;
+    DevBuf<AlignState> d_state;
     // leading-tail chains (k_pass_lead): the second state / partials buffer of the ping-pong and the parity of the next
     // kernel of the align in flight (kernel j reads state j & 1, writes state (j + 1) & 1, writes partials j & 1)
-    AlignState* d_state2 = nullptr;
+    DevBuf<AlignState> d_state2;
     int lead = 0, lead_par = 0;
     bool no_lead = false;  // batched replay: several aligns in flight share the CUs, the redundant tails would cost CU time
-    AlignState* h_state = nullptr;  // pinned (coherent), written by k_readback
+    Pinned<AlignState> h_state;  // coherent, written by k_readback
     // read-back words (pinned, coherent): [0] sequence number of the last finished round, [1..2] device clock of the
     // align's start / that round's end (100 MHz); d_clk[0]: the start stamp k_align_init takes
-    unsigned long long* h_rb = nullptr;
-    unsigned long long* d_clk = nullptr;
+    Pinned<unsigned long long[]> h_rb;
+    DevBuf<unsigned long long> d_clk;
     unsigned long long rb_seq = 0, al_seq = 0;
     DevBuf<double> partials;
     DevBuf<double> partials2;  // leading-tail chains: the other partials buffer
@@ -256,43 +343,17 @@ struct ndt_ctx {
     double gauss_cur[3] = {0.0, 0.0, 0.0};
     DevBuf<double> reduce_out;
     DevBuf<unsigned> counter;           // last-workgroup ticket of the pass epilogue (re-armed by the last workgroup)
-    PassRecordDev* d_hist = nullptr;
+    DevBuf<PassRecordDev> d_hist;
     int hist_cap = kMaxHistory;
     DevBuf<float4> out_cloud;
-    DevBuf<unsigned long long> ts;      // per-pass kTsStride s_memrealtime stamps (profiling)
-    double prof_phase_sum[7] = {0, 0, 0, 0, 0, 0, 0};
-    int prof_phase_count = 0;
-    double prof_body_sum[5] = {0, 0, 0, 0, 0};
-    int prof_body_count = 0;
-    double prof_tail_sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int prof_tail_count = 0;
-    unsigned long long* h_ts = nullptr;  // pinned copies, filled by k_readback before the align's sync
-    PassRecordDev* h_hist = nullptr;
-    int h_prof_cap = 0;
+    PassProf prof;
     bool have_result = false;
-    // point-to-point ICP (ndt_icp_align): the cumulative cloud X, per-point match / d2 of the last pass, the pass
-    // partials and ticket, the device state and history, pinned state copies ([0] read back, [1] the initial state);
-    // last_icp: the result have_result speaks of is the ICP's (icp_final), not the NDT align's (h_state->T)
-    DevBuf<float4> icp_x;
-    DevBuf<int> icp_match;
-    DevBuf<float> icp_d2;
-    DevBuf<double> icp_part;
-    DevBuf<unsigned> icp_ticket;
-    IcpState* d_icp = nullptr;
-    IcpState* h_icp = nullptr;
-    IcpRecordDev* d_icp_hist = nullptr;
-    bool icp_used = false;              // the fit index of this ctx carries the points' original indices from now on
-    bool last_icp = false;
-    float icp_final[16] = {0};
-    int icp_n = 0;                      // source points of the last ICP align
-    std::vector<IcpRecordDev> icp_hist;
-    hipGraphExec_t icp_graph = nullptr;
-    long long icp_graph_key[12] = {0};
+    IcpRun icp;
     // graph cache: a few captured chains (different slot counts / buffers), round-robin replacement
     static constexpr int kGraphKey = 23;
     static constexpr int kGraphCache = 64;
     struct GraphEntry {
-        hipGraphExec_t exec = nullptr;
+        GraphExec exec;
         long long key[kGraphKey] = {0};
     };
     GraphEntry graphs[kGraphCache];  // scans of a few neighbouring size buckets (geom_points) x both lead parities
@@ -300,16 +361,11 @@ struct ndt_ctx {
     int last_passes = 0;                // passes of the previous align: sizes the first graph round of the next
     // timing
     bool built_since_align = false;  // ms_build: a target build was queued since the last align
-    std::vector<hipEvent_t> pass_ev;
-    bool profiling = false;
-    double ms_build = 0, ms_align = 0, ms_pass_avg = 0, pass_bytes_avg = 0;
-    double prof_ms_sum = 0, prof_bytes_sum = 0;
-    long long prof_count = 0;
-    std::vector<PassRecordDev> last_hist;
+    double ms_build = 0, ms_align = 0;
     // align in flight (align_enqueue -> align_finish)
     bool al_inflight = false, al_mt = false;
     int al_full = 0, al_slots = 0;
-    // helper contexts of the batched replay (one stream each), created on first use
+    // helper contexts of the batched replay (one stream each), created on first use; ndt_destroy destroys them first
     std::vector<ndt_ctx*> helpers;
 };
 
@@ -318,10 +374,10 @@ namespace ndt::host {
 // sets the error text of the call (the ctx's, or on a side lane's host thread that thread's own) and returns st
 ndt_status fail(ndt_ctx* c, ndt_status st, const std::string& msg);
 
-inline Lane main_lane(ndt_ctx* c) { return Lane{c->stream, c->s}; }
+inline Lane main_lane(ndt_ctx* c) { return Lane{c->stream.get(), c->s}; }
 
 // final_transformation_ of the last align, NDT or ICP (valid while have_result)
-inline const float* last_final(const ndt_ctx* c) { return c->last_icp ? c->icp_final : c->h_state->T; }
+inline const float* last_final(const ndt_ctx* c) { return c->icp.last ? c->icp.final_tf : c->h_state->T; }
 
 #define HIPCHK(ctx, expr)                                                                       \
     do {                                                                                        \
@@ -330,13 +386,14 @@ inline const float* last_final(const ndt_ctx* c) { return c->last_icp ? c->icp_f
             return fail(ctx, NDT_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));   \
     } while (0)
 
+// frees early (a DevBuf otherwise lives as long as its owner)
+template <typename T> void release(DevBuf<T>& b) { DevBuf<T> gone(std::move(b)); }
+
 template <typename T> ndt_status ensure(ndt_ctx* c, DevBuf<T>& b, size_t n) {
     if (n == 0) n = 1;
     if (b.cap >= n) return NDT_OK;
     const size_t want = std::max(n, b.cap + b.cap / 2);
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
+    release(b);
     if (hipMalloc(&b.p, want * sizeof(T)) != hipSuccess) {
         b.p = nullptr;
         return fail(c, NDT_ENOMEM, "hipMalloc failed");
@@ -345,18 +402,40 @@ template <typename T> ndt_status ensure(ndt_ctx* c, DevBuf<T>& b, size_t n) {
     return NDT_OK;
 }
 
-// frees early (a DevBuf otherwise lives as long as its owner)
-template <typename T> void release(DevBuf<T>& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
-
 #define TRY(expr)                          \
     do {                                   \
         ndt_status _s = (expr);            \
         if (_s != NDT_OK) return _s;       \
     } while (0)
+
+// Creation into an owner: the owner is set only when the runtime call succeeded (n elements of pinned memory with
+// hipHostMalloc's flags; an event with hipEventCreateWithFlags's; a non-blocking stream of the given priority)
+template <typename T> ndt_status make_pinned(ndt_ctx* c, Pinned<T>& out, size_t n, unsigned flags) {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, n * sizeof(std::remove_extent_t<T>), flags) != hipSuccess) return fail(c, NDT_ENOMEM, "hipHostMalloc failed");
+    out.reset(static_cast<std::remove_extent_t<T>*>(p));
+    return NDT_OK;
+}
+inline ndt_status make_event(ndt_ctx* c, Event& out, unsigned flags) {
+    hipEvent_t e = nullptr;
+    HIPCHK(c, hipEventCreateWithFlags(&e, flags));
+    out.reset(e);
+    return NDT_OK;
+}
+inline ndt_status make_stream(ndt_ctx* c, Stream& out, int priority) {
+    hipStream_t st = nullptr;
+    HIPCHK(c, hipStreamCreateWithPriority(&st, hipStreamNonBlocking, priority));
+    out.reset(st);
+    return NDT_OK;
+}
+
+// the caller-set options handed to a helper context of the batched replay; tile_tickets stays set once a look-back of
+// the helper's own timed out
+inline void hand_options(ndt_ctx* h, const ndt_ctx* c) {
+    const bool sticky = h->opt.tile_tickets;
+    h->opt = c->opt;
+    h->opt.tile_tickets = sticky || c->opt.tile_tickets;
+}
 
 inline ndt_status set_dev(ndt_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
@@ -391,10 +470,12 @@ ndt_status upload_points(ndt_ctx* c, DevBuf<float4>& dst, const float* xyz, size
 void invalidate_graph(ndt_ctx* c);
 ndt_status copy16(ndt_ctx* c, hipStream_t stream, void* dst, const void* src, size_t bytes);
 ndt_status flush_source(ndt_ctx* c);
-ndt_status capture_graph(ndt_ctx* c, const char* end_what, const std::function<ndt_status()>& body, hipGraphExec_t* out);
+ndt_status capture_graph(ndt_ctx* c, const char* end_what, const std::function<ndt_status()>& body, GraphExec* out);
 // host_lanes.hip
 ndt_status main_after_fit(ndt_ctx* c, bool source);
 ndt_status enqueue_nn_index(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, float cell, NNIndex& ix, bool want_idx = false);
 ndt_status ensure_fit_index(ndt_ctx* c);
+// host_sc.hip
+ndt_status reserve_slots(ndt_ctx* c, SlotArrays& a, size_t size, size_t need, std::initializer_list<size_t> slot_bytes, const char* what);
 
 }  // namespace ndt::host

@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._ctxobj import _CtxObject
 from ._lib import IcpParams, IcpRecord, IcpResult, check
 from .ndt import NormalDistributionsTransform, _fp
 
@@ -27,38 +28,16 @@ __all__ = ["IterativeClosestPoint", "refine_loop", "get_transformation", "ICP_ST
 ICP_STATES = ("NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES")
 
 
-class IterativeClosestPoint:
+class IterativeClosestPoint(_CtxObject):
     """pcl::IterativeClosestPoint on MI355X.  The operator runs on a registration context: its own, or the one of an
     existing NormalDistributionsTransform (`registration=`), whose target, source and nearest-neighbour index it then
     shares (the context's resolution is the index cell size)."""
 
     def __init__(self, device: int = 0, registration: NormalDistributionsTransform | None = None):
-        self._own = registration is None
-        self._reg = NormalDistributionsTransform(device) if registration is None else registration
-        self._lib = self._reg._lib
-        self._params = IcpParams()
-        check(self._lib.ndt_icp_default_params(C.byref(self._params)))
+        super().__init__(device, registration)
+        self._params = self._default_params(IcpParams, "ndt_icp_default_params", {})
         self._result = IcpResult()
         self._has_result = False
-
-    def close(self):
-        if self._own and self._reg is not None:
-            self._reg.close()
-        self._reg = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def registration(self) -> NormalDistributionsTransform:
-        return self._reg
-
-    @property
-    def ctx(self):
-        return self._reg.ctx
 
     # ------------------------------------------------------------------ parameters (pcl::Registration)
     def setMaxCorrespondenceDistance(self, d: float):

@@ -18,6 +18,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._ctxobj import _CtxObject
 from ._lib import IscParams, IscResult, check
 from .ndt import NormalDistributionsTransform, _dp, _fp
 
@@ -53,22 +54,17 @@ def _pos(pose_xyz) -> np.ndarray:
     return p
 
 
-class ISCGeneration:
+class ISCGeneration(_CtxObject):
     """ISCGeneration on MI355X.  It runs on a registration context: its own, or the one of an existing
     NormalDistributionsTransform (`registration=`), whose device and stream it then shares.  The parameters (IscParams
     fields) are fixed once the first descriptor is stored: the database layout depends on them."""
 
+    _DESTROY = "ndt_isc_destroy"
+    _WHAT = "ISC"
+
     def __init__(self, device: int = 0, registration: NormalDistributionsTransform | None = None, **params):
-        self._own = registration is None
-        self._reg = NormalDistributionsTransform(device) if registration is None else registration
-        self._lib = self._reg._lib
-        self._isc = None
-        self._params = IscParams()
-        check(self._lib.ndt_isc_default_params(C.byref(self._params)))
-        for k, v in params.items():
-            if k not in _PARAM_NAMES:
-                raise TypeError(f"unknown ISC parameter {k!r}")
-            setattr(self._params, k, v)
+        super().__init__(device, registration)
+        self._params = self._default_params(IscParams, "ndt_isc_default_params", params)
         self._create()
         self._colors = color_projection()
         self._last = IscResult()
@@ -77,41 +73,12 @@ class ISCGeneration:
     def _create(self):
         isc = C.c_void_p()
         check(self._lib.ndt_isc_create(self.ctx, C.byref(self._params), C.byref(isc)), self.ctx)
-        if self._isc:
-            self._lib.ndt_isc_destroy(self._isc)
-        self._isc = isc
-
-    # ------------------------------------------------------------------ lifetime
-    def close(self):
-        if getattr(self, "_isc", None):
-            self._lib.ndt_isc_destroy(self._isc)  # before its context
-            self._isc = None
-        if self._own and self._reg is not None:
-            self._reg.close()
-        self._reg = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def registration(self) -> NormalDistributionsTransform:
-        return self._reg
-
-    @property
-    def ctx(self):
-        return self._reg.ctx
+        if self._handle:
+            self._lib.ndt_isc_destroy(self._handle)
+        self._handle = isc
 
     def __len__(self) -> int:
-        return int(self._lib.ndt_isc_size(self._isc))
+        return int(self._lib.ndt_isc_size(self._handle))
 
     # ------------------------------------------------------------------ parameters
     def init_param(self, rings: int, sectors: int, max_dis: float):
@@ -142,14 +109,14 @@ class ISCGeneration:
         if a.ndim != 2 or a.shape[1] < 4:
             raise ValueError("expected (N, 4) x,y,z,intensity")
         idx = C.c_int()
-        check(self._lib.ndt_isc_add(self._isc, _fp(a), a.shape[0], a.shape[1] * 4, 3, _dp(_pos(pose_xyz)), C.byref(idx)), self.ctx)
+        check(self._lib.ndt_isc_add(self._handle, _fp(a), a.shape[0], a.shape[1] * 4, 3, _dp(_pos(pose_xyz)), C.byref(idx)), self.ctx)
         return idx.value
 
     def makeAndSavedecDevice(self, d_ptr: int, n: int, pose_xyz) -> int:
         """The same of a device-resident float4 x,y,z,intensity cloud (no transfer); it stays unmodified until the next
         detection."""
         idx = C.c_int()
-        check(self._lib.ndt_isc_add_device(self._isc, C.c_void_p(d_ptr), int(n), _dp(_pos(pose_xyz)), C.byref(idx)), self.ctx)
+        check(self._lib.ndt_isc_add_device(self._handle, C.c_void_p(d_ptr), int(n), _dp(_pos(pose_xyz)), C.byref(idx)), self.ctx)
         return idx.value
 
     def add_descriptor(self, desc, pose_xyz) -> int:
@@ -158,18 +125,18 @@ class ISCGeneration:
         if d.shape != self.shape:
             raise ValueError(f"a descriptor is {self.shape[0]} x {self.shape[1]}")
         idx = C.c_int()
-        check(self._lib.ndt_isc_add_descriptor(self._isc, d.ctypes.data_as(_UP), _dp(_pos(pose_xyz)), C.byref(idx)), self.ctx)
+        check(self._lib.ndt_isc_add_descriptor(self._handle, d.ctypes.data_as(_UP), _dp(_pos(pose_xyz)), C.byref(idx)), self.ctx)
         return idx.value
 
     def descriptor(self, i: int) -> np.ndarray:
         d = np.empty(self.shape, np.uint8)
-        check(self._lib.ndt_isc_get(self._isc, int(i), d.ctypes.data_as(_UP), None, None), self.ctx)
+        check(self._lib.ndt_isc_get(self._handle, int(i), d.ctypes.data_as(_UP), None, None), self.ctx)
         return d
 
     def position(self, i: int) -> tuple[np.ndarray, float]:
         """(position as stored, travel distance) of keyframe i."""
         p, t = np.empty(3, np.float64), C.c_double()
-        check(self._lib.ndt_isc_get(self._isc, int(i), None, _dp(p), C.byref(t)), self.ctx)
+        check(self._lib.ndt_isc_get(self._handle, int(i), None, _dp(p), C.byref(t)), self.ctx)
         return p, t.value
 
     def getLastISCMONO(self) -> np.ndarray:
@@ -184,22 +151,22 @@ class ISCGeneration:
         """(is_loop, geo_score, inten_score) of stored descriptors i and j; inten_score is computed whatever the
         geometry score is."""
         geo, inten, angle, loop = C.c_double(), C.c_double(), C.c_int(), C.c_int()
-        check(self._lib.ndt_isc_pair(self._isc, int(i), int(j), C.byref(geo), C.byref(angle), C.byref(inten), C.byref(loop)), self.ctx)
+        check(self._lib.ndt_isc_pair(self._handle, int(i), int(j), C.byref(geo), C.byref(angle), C.byref(inten), C.byref(loop)), self.ctx)
         return bool(loop.value), geo.value, inten.value
 
     def calculate_geometry_dis(self, i: int, j: int) -> tuple[float, int]:
         geo, angle = C.c_double(), C.c_int()
-        check(self._lib.ndt_isc_pair(self._isc, int(i), int(j), C.byref(geo), C.byref(angle), None, None), self.ctx)
+        check(self._lib.ndt_isc_pair(self._handle, int(i), int(j), C.byref(geo), C.byref(angle), None, None), self.ctx)
         return geo.value, angle.value
 
     def calculate_intensity_dis(self, i: int, j: int, angle: int) -> float:
         inten = C.c_double()
-        check(self._lib.ndt_isc_intensity(self._isc, int(i), int(j), int(angle), C.byref(inten)), self.ctx)
+        check(self._lib.ndt_isc_intensity(self._handle, int(i), int(j), int(angle), C.byref(inten)), self.ctx)
         return inten.value
 
     def detectLoopClosureID(self) -> tuple[int, float]:
         """(prev, float(curr)) or (-1, 0.0), the reference's std::pair<int, float>."""
-        check(self._lib.ndt_isc_detect(self._isc, C.byref(self._last)), self.ctx)
+        check(self._lib.ndt_isc_detect(self._handle, C.byref(self._last)), self.ctx)
         if self._last.loop_id == -1:
             return -1, 0.0
         return int(self._last.loop_id), float(np.float32(self._last.curr_id))
@@ -214,7 +181,7 @@ class ISCGeneration:
         if q.ndim != 1:
             raise ValueError("query is 1-D")
         out = (IscResult * max(1, len(q)))()
-        check(self._lib.ndt_isc_detect_batch(self._isc, q.ctypes.data_as(C.POINTER(C.c_int)), len(q), out), self.ctx)
+        check(self._lib.ndt_isc_detect_batch(self._handle, q.ctypes.data_as(C.POINTER(C.c_int)), len(q), out), self.ctx)
         return [_record(out[i]) for i in range(len(q))]
 
 

@@ -21,6 +21,7 @@ import math
 import numpy as np
 
 from . import synth
+from ._ctxobj import _CtxObject
 from ._lib import PgoParams, PgoRecord, PgoResult, check
 from .ndt import NormalDistributionsTransform, _dp
 
@@ -49,58 +50,27 @@ def _inv(T: np.ndarray) -> np.ndarray:
     return out
 
 
-class PoseGraph:
+class PoseGraph(_CtxObject):
     """The pose graph of pgo_node on MI355X.  It runs on a registration context: its own, or the one of an existing
     NormalDistributionsTransform (`registration=`), whose device and stream it then shares.  **params are
     ndt_pgo_params fields: max_iter, step_eps, cg_max_iter, cg_rtol, prior_var, odom_var."""
 
+    _DESTROY = "ndt_pgo_destroy"
+    _WHAT = "pose-graph"
+
     def __init__(self, device: int = 0, registration: NormalDistributionsTransform | None = None, **params):
-        self._own = registration is None
-        self._reg = NormalDistributionsTransform(device) if registration is None else registration
-        self._lib = self._reg._lib
-        self._params = PgoParams()
-        check(self._lib.ndt_pgo_default_params(C.byref(self._params)))
-        for k, v in params.items():
-            if k not in _PARAM_NAMES:
-                raise TypeError(f"unknown pose-graph parameter {k!r}")
-            if k in ("prior_var", "odom_var"):
-                v = (C.c_double * 6)(*np.broadcast_to(np.asarray(v, np.float64), (6,)))
-            setattr(self._params, k, v)
+        super().__init__(device, registration)
+
+        def six(k, v):  # a variance: one value for all six components, or six
+            return (C.c_double * 6)(*np.broadcast_to(np.asarray(v, np.float64), (6,))) if k.endswith("_var") else v
+
+        self._params = self._default_params(PgoParams, "ndt_pgo_default_params", params, six)
         pg = C.c_void_p()
         check(self._lib.ndt_pgo_create(self.ctx, C.byref(self._params), C.byref(pg)), self.ctx)
-        self._pg = pg
-
-    # ------------------------------------------------------------------ lifetime
-    def close(self):
-        if getattr(self, "_pg", None):
-            self._lib.ndt_pgo_destroy(self._pg)  # before its context
-            self._pg = None
-        if getattr(self, "_own", False) and self._reg is not None:
-            self._reg.close()
-        self._reg = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def registration(self) -> NormalDistributionsTransform:
-        return self._reg
-
-    @property
-    def ctx(self):
-        return self._reg.ctx
+        self._handle = pg
 
     def __len__(self) -> int:
-        return int(self._lib.ndt_pgo_size(self._pg))
+        return int(self._lib.ndt_pgo_size(self._handle))
 
     def params(self) -> dict:
         return {k: (list(getattr(self._params, k)) if k.endswith("_var") else getattr(self._params, k)) for k in _PARAM_NAMES}
@@ -110,19 +80,19 @@ class PoseGraph:
         """A keyframe pose (4 x 4, or (x, y, z, roll, pitch, yaw) through Pose6D2Matrix).  Node 0 gets the prior, every
         later node the odometry edge from its predecessor; the pose is the node's initial estimate."""
         idx = C.c_int()
-        check(self._lib.ndt_pgo_add_node(self._pg, _dp(_colmajor(_pose44(pose))), C.byref(idx)), self.ctx)
+        check(self._lib.ndt_pgo_add_node(self._handle, _dp(_colmajor(_pose44(pose))), C.byref(idx)), self.ctx)
         return idx.value
 
     def add_loop(self, i: int, j: int, Z, variances, robust_k: float = 1.0):
         """BetweenFactor(i, j, Z): variances is one number (pgo_node uses the ICP fitness score for all six) or six;
         robust_k the Cauchy kernel's width (pgo_node: 1; 0: Gaussian)."""
         var = np.ascontiguousarray(np.broadcast_to(np.asarray(variances, np.float64), (6,)))
-        check(self._lib.ndt_pgo_add_between(self._pg, int(i), int(j), _dp(_colmajor(_pose44(Z))), _dp(var), float(robust_k)), self.ctx)
+        check(self._lib.ndt_pgo_add_between(self._handle, int(i), int(j), _dp(_colmajor(_pose44(Z))), _dp(var), float(robust_k)), self.ctx)
 
     def optimize(self) -> dict:
         """One optimisation from the current estimate (a later call is a warm start)."""
         r = PgoResult()
-        check(self._lib.ndt_pgo_optimize(self._pg, C.byref(r)), self.ctx)
+        check(self._lib.ndt_pgo_optimize(self._handle, C.byref(r)), self.ctx)
         return {"iterations": int(r.iterations), "converged": bool(r.converged), "cost0": float(r.cost0), "cost": float(r.cost),
                 "max_step": float(r.max_step), "cg_iterations": int(r.cg_iterations)}
 
@@ -130,7 +100,7 @@ class PoseGraph:
         """The current estimate, (n, 4, 4) f64."""
         n = len(self)
         buf = np.empty(max(1, n) * 16, np.float64)
-        check(self._lib.ndt_pgo_get_poses(self._pg, _dp(buf), n, None), self.ctx)
+        check(self._lib.ndt_pgo_get_poses(self._handle, _dp(buf), n, None), self.ctx)
         return buf[:n * 16].reshape(n, 4, 4).transpose(0, 2, 1).copy()
 
     def poses6d(self) -> np.ndarray:
@@ -144,17 +114,17 @@ class PoseGraph:
     def weights(self) -> np.ndarray:
         """The final robust weight of every loop factor of the last optimize(), in the order they were added."""
         n = C.c_int()
-        check(self._lib.ndt_pgo_get_weights(self._pg, None, 0, C.byref(n)), self.ctx)
+        check(self._lib.ndt_pgo_get_weights(self._handle, None, 0, C.byref(n)), self.ctx)
         buf = np.empty(max(1, n.value), np.float64)
-        check(self._lib.ndt_pgo_get_weights(self._pg, _dp(buf), n.value, None), self.ctx)
+        check(self._lib.ndt_pgo_get_weights(self._handle, _dp(buf), n.value, None), self.ctx)
         return buf[:n.value].copy()
 
     def history(self) -> list[dict]:
         """Per step of the last optimize(): the cost before it, max|d| and the CG iterations it took."""
         n = C.c_int()
-        check(self._lib.ndt_pgo_history(self._pg, None, 0, C.byref(n)), self.ctx)
+        check(self._lib.ndt_pgo_history(self._handle, None, 0, C.byref(n)), self.ctx)
         buf = (PgoRecord * max(1, n.value))()
-        check(self._lib.ndt_pgo_history(self._pg, buf, n.value, None), self.ctx)
+        check(self._lib.ndt_pgo_history(self._handle, buf, n.value, None), self.ctx)
         return [{"cost": float(buf[i].cost), "max_step": float(buf[i].max_step), "cg_iterations": int(buf[i].cg_iterations)}
                 for i in range(n.value)]
 

@@ -18,6 +18,7 @@ import math
 
 import numpy as np
 
+from ._ctxobj import _CtxObject
 from ._lib import ScParams, ScResult, check
 from .icp import refine_loop
 from .isc import detect_loops_isc
@@ -36,66 +37,29 @@ def _record(r: ScResult) -> dict:
             "cand_shift": [int(v) for v in r.cand_shift[:n]]}
 
 
-class SCManager:
+class SCManager(_CtxObject):
     """SCManager on MI355X.  It runs on a registration context: its own, or the one of an existing
     NormalDistributionsTransform (`registration=`), whose device and stream it then shares."""
 
+    _DESTROY = "ndt_sc_destroy"
+    _WHAT = "Scan Context"
+
     def __init__(self, device: int = 0, registration: NormalDistributionsTransform | None = None, **params):
-        self._own = registration is None
-        self._reg = NormalDistributionsTransform(device) if registration is None else registration
-        self._lib = self._reg._lib
-        self._params = ScParams()
-        check(self._lib.ndt_sc_default_params(C.byref(self._params)))
-        for k, v in params.items():
-            if k not in _PARAM_NAMES:
-                raise TypeError(f"unknown Scan Context parameter {k!r}")
-            setattr(self._params, k, v)
+        super().__init__(device, registration)
+        self._params = self._default_params(ScParams, "ndt_sc_default_params", params)
         sc = C.c_void_p()
         check(self._lib.ndt_sc_create(self.ctx, C.byref(self._params), C.byref(sc)), self.ctx)
-        self._sc = sc
+        self._handle = sc
         self._last = ScResult()
         self._last.loop_id = -1
 
-    # ------------------------------------------------------------------ lifetime
-    def close(self):
-        if getattr(self, "_sc", None):
-            self._lib.ndt_sc_destroy(self._sc)  # before its context
-            self._sc = None
-        if self._own and self._reg is not None:
-            self._reg.close()
-        self._reg = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def registration(self) -> NormalDistributionsTransform:
-        return self._reg
-
-    @property
-    def ctx(self):
-        return self._reg.ctx
-
     def __len__(self) -> int:
-        return int(self._lib.ndt_sc_size(self._sc))
+        return int(self._lib.ndt_sc_size(self._handle))
 
     # ------------------------------------------------------------------ parameters
     def set_params(self, **params):
-        new = ScParams.from_buffer_copy(self._params)
-        for k, v in params.items():
-            if k not in _PARAM_NAMES:
-                raise TypeError(f"unknown Scan Context parameter {k!r}")
-            setattr(new, k, v)
-        check(self._lib.ndt_sc_set_params(self._sc, C.byref(new)), self.ctx)
+        new = self._with_overrides(ScParams.from_buffer_copy(self._params), params)
+        check(self._lib.ndt_sc_set_params(self._handle, C.byref(new)), self.ctx)
         self._params = new
 
     def params(self) -> dict:
@@ -109,13 +73,13 @@ class SCManager:
         """Descriptor, ring key and sector key of a host cloud ((N, >=3) floats or PointXYZI records); returns its index."""
         buf, stride = as_points(cloud)
         idx = C.c_int()
-        check(self._lib.ndt_sc_add(self._sc, _fp(buf), len(buf) if buf.ndim == 2 else buf.size * 4 // stride, stride, C.byref(idx)), self.ctx)
+        check(self._lib.ndt_sc_add(self._handle, _fp(buf), len(buf) if buf.ndim == 2 else buf.size * 4 // stride, stride, C.byref(idx)), self.ctx)
         return idx.value
 
     def makeAndSaveScancontextAndKeysDevice(self, d_ptr: int, n: int) -> int:
         """The same of a device-resident float4 cloud (no transfer); it stays unmodified until the next detection."""
         idx = C.c_int()
-        check(self._lib.ndt_sc_add_device(self._sc, C.c_void_p(d_ptr), int(n), C.byref(idx)), self.ctx)
+        check(self._lib.ndt_sc_add_device(self._handle, C.c_void_p(d_ptr), int(n), C.byref(idx)), self.ctx)
         return idx.value
 
     def saveScancontextAndKeys(self, desc) -> int:
@@ -124,14 +88,14 @@ class SCManager:
             raise ValueError("a descriptor is 20 x 60")
         colmajor = np.ascontiguousarray(d.T).reshape(-1)
         idx = C.c_int()
-        check(self._lib.ndt_sc_add_descriptor(self._sc, _dp(colmajor), C.byref(idx)), self.ctx)
+        check(self._lib.ndt_sc_add_descriptor(self._handle, _dp(colmajor), C.byref(idx)), self.ctx)
         return idx.value
 
     def _get(self, i: int):
         desc = np.empty(N_RING * N_SECTOR, np.float64)
         rk = np.empty(N_RING, np.float32)
         sk = np.empty(N_SECTOR, np.float64)
-        check(self._lib.ndt_sc_get(self._sc, int(i), _dp(desc), _fp(rk), _dp(sk)), self.ctx)
+        check(self._lib.ndt_sc_get(self._handle, int(i), _dp(desc), _fp(rk), _dp(sk)), self.ctx)
         return desc.reshape(N_SECTOR, N_RING).T.copy(), rk, sk
 
     def polarcontext(self, i: int) -> np.ndarray:
@@ -149,11 +113,11 @@ class SCManager:
     # ------------------------------------------------------------------ detection
     def distanceBtnScanContext(self, i: int, j: int) -> tuple[float, int]:
         dist, shift = C.c_double(), C.c_int()
-        check(self._lib.ndt_sc_distance(self._sc, int(i), int(j), C.byref(dist), C.byref(shift)), self.ctx)
+        check(self._lib.ndt_sc_distance(self._handle, int(i), int(j), C.byref(dist), C.byref(shift)), self.ctx)
         return dist.value, shift.value
 
     def detectLoopClosureID(self) -> tuple[int, np.float32]:
-        check(self._lib.ndt_sc_detect(self._sc, C.byref(self._last)), self.ctx)
+        check(self._lib.ndt_sc_detect(self._handle, C.byref(self._last)), self.ctx)
         return int(self._last.loop_id), np.float32(self._last.yaw_diff)
 
     def last_result(self) -> dict:
@@ -168,7 +132,7 @@ class SCManager:
             raise ValueError("query and n_search are 1-D and of equal length")
         out = (ScResult * max(1, len(q)))()
         ip = C.POINTER(C.c_int)
-        check(self._lib.ndt_sc_detect_batch(self._sc, q.ctypes.data_as(ip), ns.ctypes.data_as(ip), len(q), out), self.ctx)
+        check(self._lib.ndt_sc_detect_batch(self._handle, q.ctypes.data_as(ip), ns.ctypes.data_as(ip), len(q), out), self.ctx)
         return [_record(out[i]) for i in range(len(q))]
 
 
