@@ -30,6 +30,16 @@ def pose_err(T, Tref):
     return float(np.linalg.norm(d[:3, 3])), ang
 
 
+def f32_transform(T, pts):
+    """pcl::transformPointCloud in float32: ((m0*x + m1*y) + m2*z) + m3."""
+    T = np.asarray(T, np.float32)
+    p = np.asarray(pts, np.float32)
+    out = np.empty_like(p[:, :3])
+    for r in range(3):
+        out[:, r] = ((T[r, 0] * p[:, 0] + T[r, 1] * p[:, 1]) + T[r, 2] * p[:, 2]) + T[r, 3]
+    return out
+
+
 def raw_scan(seed=21, half=90.0, n_points=40000, max_range=80.0, n_nan=50, n_outliers=200):
     """A raw HDL-64-like scan for filter_node's front end, sensor frame, (N, 4) x,y,z,intensity: LiDAR-like
     surfaces out to max_range (the 60 m crop removes some), a few non-finite points and isolated outliers in the air."""

@@ -15,7 +15,7 @@ Bars:
 import numpy as np
 import pytest
 
-from helpers import TF_TOL, X_TOL, pose_err, rel_err, small_pair
+from helpers import TF_TOL, X_TOL, f32_transform, pose_err, rel_err, small_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -261,21 +261,14 @@ def test_calculate_score(oracle, res):
     assert abs(g.calculateScore() - o.calculate_score(Tf)) <= 1e-12 * abs(o.calculate_score(Tf))
 
 
-def _f32_transform(T, pts):
-    """pcl::transformPointCloud in float32: ((m0*x + m1*y) + m2*z) + m3."""
-    T = np.asarray(T, np.float32)
-    p = np.asarray(pts, np.float32)
-    out = np.empty_like(p[:, :3])
-    for r in range(3):
-        out[:, r] = ((T[r, 0] * p[:, 0] + T[r, 1] * p[:, 1]) + T[r, 2] * p[:, 2]) + T[r, 3]
-    return out
-
-
-@pytest.mark.parametrize("res", [1.0, 0.5])
+@pytest.mark.parametrize("res", [1.0, 0.5, 0.05])
 def test_fitness_score_vs_kdtree(res):
     """getFitnessScore (pcl::Registration, odom_node.cpp:280): exact nearest neighbour over ALL target points.
     Checked against scipy's cKDTree: every device squared distance (float32, FLANN order) is the float32
-    distance to a nearest neighbour; the fitness is their mean; max_range filters squared distances."""
+    distance to a nearest neighbour; the fitness is their mean; max_range filters squared distances.
+    At res 0.05 the index doubles its cell: the 80 m x 80 m x 14.5 m target spans 1601 x 1601 x 291 cells of 0.05 m,
+    201 x 201 x 37 blocks of 8^3 cells = 765e6 keys > 2^25; 0.1 m still gives 101 x 101 x 19 x 512 = 99e6, 0.2 m fits
+    (51 x 51 x 10 x 512 = 13e6).  The target's voxel grid (1601 x 1601 x 291 = 7.5e8 < 2^31 voxels) does not overflow."""
     from scipy.spatial import cKDTree
     pair = small_pair()
 
@@ -297,7 +290,7 @@ def test_fitness_score_vs_kdtree(res):
         # guess / truth, a 27 m offset (most queries far from their neighbour) and one far outside the target box
         for T in (pair.guess, pair.true_pose, shifted(pair.guess, [25.0, -10.0, 4.0]), shifted(pair.guess, [400.0, 0.0, -50.0])):
             f, d2 = g.getFitnessScore(T=T, return_distances=True)
-            xt = _f32_transform(T, pair.source)
+            xt = f32_transform(T, pair.source)
             _, idx = tree.query(xt.astype(np.float64))
             u = tgt[idx] - xt
             ref = (u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1]) + u[:, 2] * u[:, 2]
