@@ -24,9 +24,9 @@ extern "C" {
  * (ndt_result, ndt_pass_record, ndt_pair_desc, ndt_filter_params, ndt_pass_phases' 22 doubles).  History: 1 = round 1;
  * 2 = ndt_result.solver_fallbacks appended, ndt_pass_phases 20 -> 22 doubles; 3 = the Scan Context surface (ndt_sc_params,
  * ndt_sc_result; no earlier layout changed); 4 = the pose-graph surface (ndt_pgo_params, ndt_pgo_result, ndt_pgo_record;
- * no earlier layout changed); 5 = the ISC surface (ndt_isc_params, ndt_isc_result); no earlier layout changed.  A caller
- * built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
-#define NDT_HIP_ABI_VERSION 5
+ * no earlier layout changed); 5 = the ISC surface (ndt_isc_params, ndt_isc_result); no earlier layout changed; 6 =
+ * ndt_pass_geometry (its 8 ints); no earlier layout changed.  A caller built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
+#define NDT_HIP_ABI_VERSION 6
 
 typedef struct ndt_ctx ndt_ctx;
 
@@ -428,6 +428,14 @@ ndt_status ndt_grid_leaves(ndt_ctx* ctx, int* keys, int* npts, double* mean, dou
  * target-cell order during an align, 0 keeps the caller's order (another fixed f64 summation order).  Applies to the
  * ctx and its batch helper contexts; no align may be in flight. */
 ndt_status ndt_set_pass_options(ndt_ctx* ctx, int lead_tail, int points_per_thread, int source_order);
+
+/* The launch geometry of a derivative-pass kernel for the ctx's current source, target, parameters and pass options
+ * (a test hook: the thresholds between the geometries depend on the device's CU count).  which: 0 = k_pass_direct (the
+ * last-workgroup-tail direct pass), 1 = k_pass_lead (the leading-tail direct pass), 2 = k_pass_radius.  out[0]
+ * workgroups, out[1] threads per workgroup, out[2] points per workgroup and tile, out[3] points per thread, out[4] 1 =
+ * the one-tile kernel, out[5] tiles per workgroup, out[6] groups of the two-level partial hand-off (0 = one level),
+ * out[7] workgroups per group (0 = one level).  Computed by the functions the launchers use; launches nothing. */
+ndt_status ndt_pass_geometry(ndt_ctx* ctx, int which, int out[8]);
 
 /* Target-build robustness hooks (no reference counterpart).  A target sort whose decoupled look-back timed
  * out (a predecessor tile never became resident: blockIdx.x tile order relies on each XCD dispatching its workgroups in

@@ -5,7 +5,8 @@ failure modes of its MI355X restatement).
 * A target sort that flags an error is re-run, and the registration goes on: forced here by launching fewer radix passes
   than the key needs (ndt_set_build_options(radix_passes=1): the last launched pass flags it), which takes the same
   path as a decoupled look-back that timed out (the ticket-ordered re-run is checked through tile_tickets=1) — grid and
-  align bit-identical to an unforced ctx.
+  align bit-identical to an unforced ctx.  With a source of >= 262 144 points the align's own source-order sort runs the
+  same radix passes and is covered by the re-run too: forced, and by a map grown past the predicted key width.
 * The radix passes a target sort launches follow the previous grid's key width (C2's 23-bit keys: three, no empty fourth).
 * The align-graph cache (64 chains) cycled through more than 64 source-size buckets on one ctx while getFitnessScore's
   side lane runs beside every align: every result equals a fresh ctx's.
@@ -63,6 +64,64 @@ def test_flagged_build_is_rerun_by_the_align():
     assert f.build_stats()["rerun"] == 2
     ref.close()
     f.close()
+
+
+def test_flagged_build_is_rerun_with_a_sorted_source():
+    """The same with a source of 266 240 points, which the align sorts into target-cell order with the radix passes of
+    the target build: the forced single pass flags that sort as well, and the re-run (build and align) covers it with
+    all four passes — a re-run that covered the build alone failed with "target build failed twice"."""
+    pair = small_pair(seed=5, half=60.0, n_source=266240, max_range=40.0)
+    ref = _ctx(pair)
+    ref.align(pair.guess, want_output=False)
+    r0 = ref.result()
+    f = _ctx(pair, radix_passes=1)
+    assert f.build_stats()["radix_passes"] == 1
+    f.align(pair.guess, want_output=False)
+    r1 = f.result()
+    st = f.build_stats()
+    assert st["rerun"] == 1 and st["rerun_lookback"] == 0 and st["tile_tickets"] == 0, st
+    assert np.array_equal(r0["final_tf"], r1["final_tf"]) and r0["n_pairs"] == r1["n_pairs"]
+    for a, b in zip(ref.history(), f.history()):
+        assert np.array_equal(a["x"], b["x"]) and a["pairs"] == b["pairs"]
+    _same_grid(ref, f)
+    # a synchronous grid reader (no align in between) re-runs a flagged build too
+    f.setInputTarget(pair.target)
+    _same_grid(ref, f)
+    assert f.build_stats()["rerun"] == 2
+    ref.close()
+    f.close()
+
+
+def test_map_grown_past_the_predicted_key_width_with_a_sorted_source():
+    """A ctx whose last grid had 13-bit keys (two radix passes predicted) gets a target of 19-bit keys (three) and a
+    266 240-point source: the align finds the build flagged, and its re-run — build, source sort and align — gives bit
+    for bit what a fresh ctx gives on the same clouds; afterwards the prediction follows the new grid."""
+    small = small_pair(seed=5, half=15.0, max_range=10.0, n_source=4000)
+    big = small_pair(seed=5, half=60.0, max_range=40.0, n_source=266240)
+    g = _ctx(small)
+    g.align(small.guess, want_output=False)
+    assert g.build_stats()["radix_passes"] == 2
+    g.setInputTarget(big.target)
+    g.setInputSource(big.source)
+    g.align(big.guess, want_output=False)
+    rg, hg = g.result(), g.history()
+    st = g.build_stats()
+    assert st["rerun"] == 1 and st["rerun_lookback"] == 0 and st["tile_tickets"] == 0, st
+    assert st["radix_passes"] == 3
+    ref = _ctx(big)
+    ref.align(big.guess, want_output=False)
+    r0, h0 = ref.result(), ref.history()
+    assert ref.build_stats()["rerun"] == 0
+    _same_grid(ref, g)
+    assert np.array_equal(r0["final_tf"], rg["final_tf"]) and r0["n_pairs"] == rg["n_pairs"]
+    assert len(h0) == len(hg) and len(hg) > 0
+    for a, b in zip(h0, hg):
+        assert a["kind"] == b["kind"] and a["newton_iter"] == b["newton_iter"] and a["pairs"] == b["pairs"]
+        for k in ("x", "g", "H"):
+            assert np.array_equal(a[k], b[k]), k
+        assert a["score"] == b["score"]
+    ref.close()
+    g.close()
 
 
 def test_ticket_ordered_build_matches():

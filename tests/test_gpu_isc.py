@@ -83,7 +83,7 @@ EDGE_POINTS = np.array([
 # ---------------------------------------------------------------------------------------------- descriptors
 def test_abi_version():
     from xchu_slam_amd import _lib
-    assert _lib.load().ndt_abi_version() == 5
+    assert _lib.load().ndt_abi_version() == 6
 
 
 def test_descriptors():

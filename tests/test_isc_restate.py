@@ -209,7 +209,7 @@ def test_ctypes_mirrors_match_the_header(tmp_path):
         assert int(got[cname]) == ctypes.sizeof(py) == 56, cname
         for f, _ in py._fields_:
             assert int(got[f"{cname}.{f}"]) == getattr(py, f).offset, (cname, f)
-    assert _lib.ABI_VERSION == 5 and "#define NDT_HIP_ABI_VERSION 5" in hdr
+    assert _lib.ABI_VERSION == 6 and "#define NDT_HIP_ABI_VERSION 6" in hdr
     p = _lib.IscParams()
     assert _lib.load().ndt_isc_default_params(ctypes.byref(p)) == 0
     assert (p.rings, p.sectors, p.max_dis) == (R.RINGS, R.SECTORS, R.MAX_DIS)

@@ -2,6 +2,8 @@
 
 * angle_table_entry (one lane per entry of computeAngleDerivatives' tables, ndt_omp_impl.hpp:286-398) vs
   angle_table_row: bit-exact on random angles (tests/native/angle_table_check.cpp).
+* the derivative passes' launch geometry and the two-level hand-off's grouping (csrc/ndt_geom.h, ndt_types.h), swept over
+  CU counts, searches, pass options and source sizes around every threshold (tests/native/pass_geom_check.cpp).
 """
 import os
 import shutil
@@ -70,5 +72,23 @@ def test_pair_orders_match_binary_sse(tmp_path):
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-msse2", "-o", str(exe),
                     os.path.join(HERE, "native", "sse_order_check.cpp")], check=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "mismatched: 0" in out.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_pass_geometry_sweep(tmp_path):
+    """The launch geometry host_align.hip launches through (ndt_geom.h), for 1 / 8 / 104 / 256 / 304 CUs, DIRECT7 /
+    DIRECT26 / DIRECT1, points_per_thread 1 / 2 / 3, both tails and every source size within 2 of a threshold (4096,
+    768 per CU, 262 144, 393 216, 1 048 576, the powers of two to 2^23) plus a stride: the size bucket is >= the scan,
+    monotone and a whole number of its steps; every tile's points have a thread slot (ppb <= block x points per thread);
+    the workgroups' tiles cover the bucket and one-tile kernels in one tile; two points per thread only while every
+    cloud index fits 22 bits.  For every grid of 1025..32768 workgroups the two-level hand-off's group size is even (a
+    group closer loads its columns as 16-byte pairs from partials + g * G), there are at most kMaxGroups groups, the
+    last one is not empty and the group partials fit the allocation.  The geometries tests/test_gpu_pass_geometry.py
+    names are pinned for 256 CUs."""
+    exe = tmp_path / "pgc"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), os.path.join(HERE, "native", "pass_geom_check.cpp")], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "mismatched: 0" in out.stdout

@@ -343,6 +343,7 @@ SIGNATURES = {
     "ndt_pass_phases": (C.c_int, [_P, _DP]),
     "ndt_set_profiling": (C.c_int, [_P, C.c_int]),
     "ndt_set_pass_options": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "ndt_pass_geometry": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "ndt_set_build_options": (C.c_int, [_P, C.c_int, C.c_int]),
     "ndt_build_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
     "ndt_last_error": (C.c_char_p, [_P]),
@@ -362,7 +363,7 @@ SIGNATURES = {
 
 _lib = None
 # struct layouts this binding mirrors (include/ndt_hip.h NDT_HIP_ABI_VERSION); load() refuses a library built otherwise
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 def load() -> C.CDLL:

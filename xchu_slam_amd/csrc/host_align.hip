@@ -60,86 +60,15 @@ ndt_status capture_graph(ndt_ctx* c, const char* end_what, const std::function<n
 
 namespace {
 
-int pass_blocks(int n) { return std::max(1, std::min(ceil_div(n, kBlock), 2048)); }
-
-// The point count a pass chain's launch geometry is built for: the scan's size rounded up to 1/64 of its power of two
-// (<= ~1.6 % more points per workgroup), at least a multiple of 256.  The pass kernels take the real count from the align state, so one
-// captured chain serves every scan of the bucket: odom_node's filtered scans change size every frame, and a chain
-// re-captured per align cost ~50 us (4 k points, 11 passes: 0.226 vs 0.178 ms per align).  Source buffers hold at least
-// this many points (the kernels prefetch up to it).
-int geom_points(int n) {
-    if (n <= 4096) return std::max(256, ceil_div(n, 256) * 256);
-    int p = 1;
-    while (p * 2 <= n) p *= 2;
-    const int step = p / 64;
-    return ceil_div(n, step) * step;
-}
-
-// Direct-pass geometry: one workgroup per CU (fewer for small clouds), each taking `rounds` tiles of ppb points
-// (ppb <= the workgroup size) so every CU carries the same share of the scan.
-struct PassGeom {
-    int nb, ppb, block;
-};
-
 bool needs_direct(const ndt_params& p) { return p.precision_mode == 0 && p.search != NDT_KDTREE; }
 bool needs_radius(const ndt_params& p, bool mt_possible) { return !needs_direct(p) || mt_possible; }
 
-// Workgroups of at most one per CU (of this ctx's share) x the pass's workgroups per CU, and at least ~64 points each
-int direct_blocks(const ndt_ctx* c, bool lead, int n, int ppt, bool one_tile = false) {
-    return std::max(1, std::min(c->n_cu * pass_wgs_per_cu(c->prm.search, lead, ppt, one_tile), ceil_div(n, 64)));
-}
-
-// Last-workgroup-tail passes of large clouds as a grid of one-tile workgroups (k_pass_direct<S, 1, true>: no tile loop,
-// three waves per SIMD, as many 256-point workgroups as the scan needs — C5's 1 M points: 3 907) whose partials are
-// summed by the two-level hand-off (pass_handoff); the alternative to the two-points-per-thread tile loop (pass_ppt2).
-// ndt_set_pass_options(points_per_thread = 3) selects it (A/B; off by default).
-bool grid_one_tile(const ndt_ctx* c) {
-    if (c->opt.ppt != 3 || c->prm.search == NDT_DIRECT26) return false;
-    return geom_points(std::max(1, c->N)) > c->n_cu * kLeadBlock1;
-}
-
-// Last-workgroup-tail passes (k_pass_direct) of DIRECT7 / DIRECT1 hold two points per thread in a tile (half the
-// tiles, the pair list packed into one word) once a workgroup walks >= 4 tiles of one point per thread (C5's 1 M-point
-// scans: pass 87 -> 81 us; at C4's 3 tiles the halved tile count loses, 27.4 -> 28.8 us).  Every cloud index must then
-// fit 22 bits.  ndt_set_pass_options(points_per_thread = 1) keeps one point per thread.
-bool pass_ppt2(const ndt_ctx* c) {
-    if (c->opt.ppt != 2 || c->prm.search == NDT_DIRECT26 || grid_one_tile(c)) return false;
-    const long long max_cloud = (long long)c->M / std::max(1, c->prm.min_points_per_voxel) + 1;
-    const int n = geom_points(std::max(1, c->N));
-    const int rounds1 = ceil_div(n, direct_blocks(c, false, n, 1) * pass_block(c->prm.search, false));
-    return max_cloud < (1ll << 22) && rounds1 >= 4;
-}
-
-// Last-workgroup-tail passes of one point per thread whose point bucket fits one tile per workgroup at three workgroups
-// per CU (C4's 120 k-point pairs): k_pass_direct<S, 1, true>, three waves per SIMD
-bool direct_one_tile(const ndt_ctx* c) {
-    if (!NDT_DIRECT_ONE_TILE || c->prm.search == NDT_DIRECT26 || pass_ppt2(c)) return false;
-    const int n = geom_points(std::max(1, c->N));
-    return (long long)n <= (long long)direct_blocks(c, false, n, 1, true) * pass_block(c->prm.search, false);
-}
-
-// leading-tail passes in one tile per workgroup (k_pass_lead<S, true>): DIRECT7 / DIRECT1 whose point bucket fits one
-// 768-point tile per CU
-bool lead_one_tile(const ndt_ctx* c) {
-    return NDT_LEAD_ONE_TILE && c->prm.search != NDT_DIRECT26 && (long long)geom_points(std::max(1, c->N)) <= (long long)c->n_cu * kLeadBlock1;
-}
-
-PassGeom direct_geom(const ndt_ctx* c, bool lead) {
-    PassGeom g;
-    g.block = pass_block(c->prm.search, lead, lead && lead_one_tile(c));
-    const int n = geom_points(std::max(1, c->N));
-    if (!lead && grid_one_tile(c)) {
-        g.nb = ceil_div(n, g.block);
-        g.ppb = g.block;
-        return g;
-    }
-    const int ppt = (!lead && pass_ppt2(c)) ? 2 : 1;
-    g.nb = direct_blocks(c, lead, n, ppt, !lead && direct_one_tile(c));
-    const int per_tile = g.block * ppt;
-    const int rounds = ceil_div(n, g.nb * per_tile);
-    g.ppb = ceil_div(n, g.nb * rounds);
-    return g;
-}
+// The launch geometry (ndt_geom.h) of this ctx's source, target, params and options
+bool grid_one_tile(const ndt_ctx* c) { return grid_one_tile(pass_shape(c)); }
+bool pass_ppt2(const ndt_ctx* c) { return pass_ppt2(pass_shape(c)); }
+bool direct_one_tile(const ndt_ctx* c) { return direct_one_tile(pass_shape(c)); }
+bool lead_one_tile(const ndt_ctx* c) { return lead_one_tile(pass_shape(c)); }
+PassGeom direct_geom(const ndt_ctx* c, bool lead) { return direct_geom(pass_shape(c), lead); }
 
 // The neighbour cache the direct passes of an align read and write (DIRECT7 only; sized by ensure_align_buffers); the
 // single-pass test hook (mode 1) runs without it
@@ -639,7 +568,13 @@ ndt_status align_finish(ndt_ctx* c) {
     if (!c->al_berr) return NDT_OK;
     const int berr = c->al_berr;
     TRY(rerun_build(c, berr));
-    TRY(align_enqueue(c, c->al_guess));
+    // the re-run align sorts its source against the new grid (enqueue_source_order) before any read-back of that grid
+    // could renew the radix prediction: all four passes for that sort too.  Once this align has read the grid back the
+    // prediction follows it again (note_grid_width in align_finish_once).
+    c->rerun_full = true;
+    ndt_status st = align_enqueue(c, c->al_guess);
+    c->rerun_full = false;
+    TRY(st);
     TRY(align_finish_once(c));
     if (c->al_berr)
         return fail(c, NDT_EDEVICE, std::string("target build failed twice (error bits ") + std::to_string(berr) + ", " +

@@ -185,6 +185,12 @@ ndt_status ndt_set_pass_options(ndt_ctx* c, int lead_tail, int points_per_thread
     return NDT_OK;
 }
 
+ndt_status ndt_pass_geometry(ndt_ctx* c, int which, int out[8]) {
+    if (!c || !out) return fail(c, NDT_EINVAL, "null argument");
+    if (!describe_pass(pass_shape(c), which, out)) return fail(c, NDT_EINVAL, "bad pass kernel index");
+    return NDT_OK;
+}
+
 ndt_status ndt_set_build_options(ndt_ctx* c, int tile_tickets, int radix_passes) {
     if (!c || tile_tickets < 0 || tile_tickets > 1 || radix_passes < 0 || radix_passes > 4) return fail(c, NDT_EINVAL, "bad build options");
     if (c->al_inflight) return fail(c, NDT_EINVAL, "an asynchronous align is in flight (ndt_align_wait first)");

@@ -746,6 +746,7 @@ __device__ __forceinline__ void after_solve_store(AlignState& st, const StepRegs
 template <int NW, int FAST = NDT_TAIL_FAST>
 __device__ __forceinline__ void tail_control(AlignState& s_st, const double* red, PassRecordDev* hist, int hist_cap,
                                              unsigned long long* ts) {
+    static_assert(FAST != 3 || NW >= 3, "fast path 3 runs the step on waves 0 and 1 and a sin / cos on wave 2");
     __shared__ double s_spec_dp[6];
     __shared__ int s_spec_fail;
     const bool spec = s_st.phase == 0 || s_st.pass_kind == PASS_FULL;

@@ -20,6 +20,7 @@
 
 #include "../../include/ndt_hip.h"
 #include "ndt_kernels.h"
+#include "ndt_geom.h"
 
 namespace ndt::host {
 
@@ -133,8 +134,6 @@ struct SlotArrays {
     std::vector<char*> arr;
     template <typename T> T* at(int k) const { return reinterpret_cast<T*>(arr[k]); }
 };
-
-inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Exact nearest-neighbour index over a cloud (block-major binning, layout 1 of k_header): the points sorted into
 // 8x8x8-cell blocks, a block table and per-occupied-block cell offsets.
@@ -295,7 +294,7 @@ struct ndt_ctx {
     // what opt.radix_force fixes); counters for ndt_build_stats
     int radix_pred = 4;
     bool build_unchecked = false;   // a target build queued whose error bits no align / settle_build has read yet
-    bool rerun_full = false;        // a re-run build: all four radix passes whatever the prediction or the hook says
+    bool rerun_full = false;        // a re-run build and its align's source sort: all four radix passes whatever the prediction or the hook says
     float al_guess[16] = {0};       // the guess of the align in flight (re-run after a flagged build)
     int al_berr = 0;                // build error bits the align's read-back found (align_finish_once)
     long long n_builds_full = 0, n_builds_merge = 0, n_builds_rerun = 0, n_rerun_lookback = 0;
@@ -375,6 +374,11 @@ namespace ndt::host {
 ndt_status fail(ndt_ctx* c, ndt_status st, const std::string& msg);
 
 inline Lane main_lane(ndt_ctx* c) { return Lane{c->stream.get(), c->s}; }
+
+// what the pass geometry (ndt_geom.h) reads of a ctx
+inline PassShape pass_shape(const ndt_ctx* c) {
+    return PassShape{c->n_cu, c->N, c->M, c->prm.search, c->prm.min_points_per_voxel, c->opt.ppt};
+}
 
 // final_transformation_ of the last align, NDT or ICP (valid while have_result)
 inline const float* last_final(const ndt_ctx* c) { return c->icp.last ? c->icp.final_tf : c->h_state->T; }

@@ -84,7 +84,10 @@ constexpr int kGroupTicketBase = 16;
 constexpr int kPassCounterWords = kGroupTicketBase + kMaxGroups * kGroupTicketStride;
 constexpr int kTwoLevelMinBlocks = 1024;
 // group partials of the two-level hand-off: [kNumAcc][kMaxGroups] doubles after the [kNumAcc][partial_stride(nb)] ones
-__host__ __device__ constexpr int group_size(int nb) { return nb / kMaxGroups >= 64 ? (nb + kMaxGroups - 1) / kMaxGroups : 64; }
+// (the group size is even: a group closer sums its columns from partials + g * G by 16-byte pairs, reduce_partials_block)
+__host__ __device__ constexpr int group_size(int nb) {
+    return nb / kMaxGroups >= 64 ? (((nb + kMaxGroups - 1) / kMaxGroups + 1) & ~1) : 64;
+}
 // profiling stamps per pass (s_memrealtime, 100 MHz): [0] start(min), [1] end(max), [2] last body done(max),
 // [3] tail acquired, [4] tail reduced, [6] state staged in LDS, [7] control step done, [5] next pass prepared
 constexpr int kTsStride = 16;

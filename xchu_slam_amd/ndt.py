@@ -325,6 +325,15 @@ class NormalDistributionsTransform:
         check(self._lib.ndt_set_pass_options(self._ctx, int(bool(lead_tail)), int(points_per_thread), int(bool(source_order))),
               self._ctx)
 
+    def pass_geometry(self, which: int = 0) -> dict:
+        """ndt_pass_geometry: the launch geometry of k_pass_direct (0), k_pass_lead (1) or k_pass_radius (2) for the
+        current source, target, parameters and pass options (include/ndt_hip.h)."""
+        out = (C.c_int * 8)()
+        check(self._lib.ndt_pass_geometry(self._ctx, int(which), out), self._ctx)
+        v = list(out)
+        return {"workgroups": v[0], "block": v[1], "ppb": v[2], "points_per_thread": v[3], "one_tile": bool(v[4]),
+                "tiles": v[5], "groups": v[6], "group_size": v[7]}
+
     def set_build_options(self, tile_tickets: bool = False, radix_passes: int = 0):
         """ndt_set_build_options: target-sort test hooks (include/ndt_hip.h)."""
         check(self._lib.ndt_set_build_options(self._ctx, int(bool(tile_tickets)), int(radix_passes)), self._ctx)
