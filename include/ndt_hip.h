@@ -412,6 +412,59 @@ ndt_status ndt_pgo_get_weights(ndt_pgo* pgo, double* w, int cap, int* n_out);
 /* One record per step of the last optimise. */
 ndt_status ndt_pgo_history(ndt_pgo* pgo, ndt_pgo_record* out, int cap, int* n_out);
 
+/* ---- Global map: what pgo_node builds three times from its keyframes and their current poses (pgo_node.cpp) — SaveMap
+ * (:620-653, every keyframe, finalMap.pcd), PublishPoseAndFrame (:744-812, every second keyframe, again as the graph
+ * changes) and LoopFindNearKeyframesCloud (:530-554, root +- 25): each keyframe moved by its pose
+ * (pcl::transformPointCloud, f32), stacked, pcl::VoxelGrid(leaf).  The keyframes live on the device once, in one
+ * growing arena of float4 x,y,z,intensity points; a build stacks any selection of them in one launch and filters it
+ * with the ctx's VoxelGrid (the restatement of DESIGN.md §2; the stacked cloud equals per-keyframe ndt_transform_device
+ * bit for bit, the map equals ndt_voxel_downsample_device of it).  Non-finite coordinates are outside the contract
+ * (filter_node removes them upstream).
+ * An ndt_map is created on a ctx, uses that ctx's device and stream, reports its errors through ndt_last_error(ctx), and
+ * is destroyed before the ctx. */
+typedef struct ndt_map ndt_map;
+
+ndt_status ndt_map_create(ndt_ctx* ctx, ndt_map** out);
+void ndt_map_destroy(ndt_map* m);
+/* keyframes stored (-1 for a NULL handle) */
+int ndt_map_size(const ndt_map* m);
+/* points held / points the arena has room for (64-bit counts, so through a pointer like every other wide result here) */
+ndt_status ndt_map_points(const ndt_map* m, long long* points);
+ndt_status ndt_map_capacity(const ndt_map* m, long long* points);
+/* Room for at least `points` points.  The arena also grows by itself, to at least twice its size, the held points
+ * moved device to device on the ctx stream: keyframe contents survive bit for bit, pointers from ndt_map_keyframe do
+ * not.  A growth that fails (NDT_ENOMEM) leaves the store as it was. */
+ndt_status ndt_map_reserve(ndt_map* m, long long points);
+/* A keyframe from a host cloud (x,y,z at the start of each stride_bytes record, intensity at float index
+ * intensity_offset; synchronises) / from a device float4 cloud (device-to-device copy on the ctx stream, no transfer;
+ * asynchronous: d_xyzi4 stays unmodified until the next synchronising call).  *index (may be NULL) = the slot it took.
+ * n = 0 is legal: an empty keyframe keeps its index. */
+ndt_status ndt_map_add(ndt_map* m, const float* xyzi, size_t n, size_t stride_bytes, int intensity_offset, int* index);
+ndt_status ndt_map_add_device(ndt_map* m, const float* d_xyzi4, size_t n, int* index);
+/* The stored keyframe on the device (valid until the next ndt_map_add[_device] / ndt_map_reserve; it can feed
+ * ndt_sc_add_device, ndt_isc_add_device, ndt_set_source_device ...) / copied to the host: out4 receives min(cap, n)
+ * points, *n_out (may be NULL) = n. */
+ndt_status ndt_map_keyframe(ndt_map* m, int index, const float** d_xyzi4, size_t* n);
+ndt_status ndt_map_get_keyframe(ndt_map* m, int index, float* out4, size_t cap, size_t* n_out);
+/* Points of a selection (what a caller buffer for ndt_map_build must hold): index[0..n_sel), NULL = 0..n_sel-1. */
+ndt_status ndt_map_count(ndt_map* m, const int* index, int n_sel, long long* total);
+/* Stack keyframes index[0..n_sel) (NULL = 0..n_sel-1), keyframe k moved by the column-major 4x4 float T16 + 16*k, in
+ * selection order, then pcl::VoxelGrid(leaf); leaf == 0: the stacked cloud itself.  d_out4 NULL: the map's own result
+ * buffer (valid until the next build); else a caller buffer with room for cap >= total points (total = ndt_map_count).
+ * *n_out = the points written.  A repeated index is stacked twice.  NDT_EINVAL: an index outside the store, a total
+ * above 2^31 - 1 points, cap < total, T16 NULL with n_sel > 0.  An empty selection or one of 0 points: NDT_OK, *n_out =
+ * 0.  NDT_EOVERFLOW: the leaf is too small for pcl::VoxelGrid's index range; the result is the stacked cloud, as
+ * pcl::VoxelGrid outputs its input then.  One k_map_stack launch whatever n_sel is; synchronises. */
+ndt_status ndt_map_build(ndt_map* m, const int* index, const float* T16, int n_sel, float leaf, float* d_out4, size_t cap,
+                         size_t* n_out);
+/* The last build into the map's own buffer, on the device / copied to the host (min(cap, n) points, *n_out = n).  A
+ * build into a caller buffer leaves it as it was; NDT_EINVAL before the first such build. */
+ndt_status ndt_map_result(ndt_map* m, const float** d_out4, size_t* n);
+ndt_status ndt_map_get(ndt_map* m, float* out4, size_t cap, size_t* n_out);
+/* The last build's launch (a test hook): out[0] workgroups (0: nothing to stack), out[1] threads per workgroup, out[2]
+ * output points a workgroup takes at a time, out[3] segments (= n_sel). */
+ndt_status ndt_map_geometry(ndt_map* m, int out[4]);
+
 /* Voxel grid inspection: header = min_b[3], max_b[3], div_b[3], divb_mul[3], n_leaves, n_cloud, overflow,
  * n_valid (16 ints).  Leaves with >= min points (the reference's KD cloud) in ascending key order. */
 ndt_status ndt_grid_info(ndt_ctx* ctx, int header[16]);

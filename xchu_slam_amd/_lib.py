@@ -316,7 +316,22 @@ SIGNATURES = {
     "ndt_pgo_get_poses": (C.c_int, [_P, _DP, C.c_int, C.POINTER(C.c_int)]),
     "ndt_pgo_get_weights": (C.c_int, [_P, _DP, C.c_int, C.POINTER(C.c_int)]),
     "ndt_pgo_history": (C.c_int, [_P, C.POINTER(PgoRecord), C.c_int, C.POINTER(C.c_int)]),
-    "ndt_fitness_score_async_cloud": (C.c_int, [_P, _FP, C.c_double, _P, C.c_size_t]),
+    "ndt_map_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "ndt_map_destroy": (None, [_P]),
+    "ndt_map_size": (C.c_int, [_P]),
+    "ndt_map_points": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "ndt_map_capacity": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "ndt_map_reserve": (C.c_int, [_P, C.c_longlong]),
+    "ndt_map_add": (C.c_int, [_P, _FP, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_int)]),
+    "ndt_map_add_device": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_int)]),
+    "ndt_map_keyframe": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "ndt_map_get_keyframe": (C.c_int, [_P, C.c_int, _FP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ndt_map_count": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_longlong)]),
+    "ndt_map_build": (C.c_int, [_P, C.POINTER(C.c_int), _FP, C.c_int, C.c_float, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ndt_map_result": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "ndt_map_get": (C.c_int, [_P, _FP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ndt_map_geometry": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "ndt_fitness_score_async_cloud":(C.c_int, [_P, _FP, C.c_double, _P, C.c_size_t]),
     "ndt_fitness_score_async_aligned": (C.c_int, [_P, C.c_double, _P, C.c_size_t]),
     "ndt_keyframe_insert_async": (C.c_int, [_P, _FP, _P, C.c_size_t, C.c_float, _P, C.c_size_t, _P, C.c_size_t]),
     "ndt_keyframe_insert_result": (C.c_int, [_P, C.POINTER(C.c_size_t)]),

@@ -2,8 +2,10 @@
 // (crop, VoxelGrid, outlier removal).
 #include "ndt_host.h"
 
-// pcl::VoxelGrid over n device points: the voxel means in out (room for n points), their count in *n_out
-static ndt_status voxel_downsample_dev(ndt_ctx* c, const float4* in, size_t n, float leaf, float4* out, size_t* n_out) {
+namespace ndt::host {
+
+// pcl::VoxelGrid over n device points: the voxel means in out (room for n points), their count in *n_out; synchronises
+ndt_status voxel_downsample_dev(ndt_ctx* c, const float4* in, size_t n, float leaf, float4* out, size_t* n_out) {
     TRY(enqueue_bin_and_sort(c, main_lane(c), in, (int)n, 1, c->d_hdr_ds.p, leaf));
     TRY(enqueue_downsample_finalize(c, main_lane(c), c->d_hdr_ds.p, in, (int)n, out));
     HIPCHK(c, hipMemcpyAsync(c->h_hdr.get(), c->d_hdr_ds.p, sizeof(GridHeader), hipMemcpyDeviceToHost, c->stream.get()));
@@ -19,6 +21,8 @@ static ndt_status voxel_downsample_dev(ndt_ctx* c, const float4* in, size_t n, f
     *n_out = (size_t)c->h_hdr->n_leaves;
     return NDT_OK;
 }
+
+}  // namespace ndt::host
 
 extern "C" {
 

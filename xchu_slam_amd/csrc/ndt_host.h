@@ -479,6 +479,8 @@ ndt_status capture_graph(ndt_ctx* c, const char* end_what, const std::function<n
 ndt_status main_after_fit(ndt_ctx* c, bool source);
 ndt_status enqueue_nn_index(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, float cell, NNIndex& ix, bool want_idx = false);
 ndt_status ensure_fit_index(ndt_ctx* c);
+// host_front_end.hip
+ndt_status voxel_downsample_dev(ndt_ctx* c, const float4* in, size_t n, float leaf, float4* out, size_t* n_out);
 // host_sc.hip
 ndt_status reserve_slots(ndt_ctx* c, SlotArrays& a, size_t size, size_t need, std::initializer_list<size_t> slot_bytes, const char* what);
 

@@ -190,9 +190,26 @@ def _submap_device(reg: NormalDistributionsTransform, keyframes, poses, idxs, le
     return d_out.value, int(n_out.value), [d_in.value, d_out.value]
 
 
+def _submap_store(store, poses, idxs, leaf: float):
+    """_submap_device from a KeyframeMap: the keyframes are resident, so the submap is one ndt_map_build into a buffer of
+    this call's own (the two submaps of a loop live side by side).  Same return value."""
+    reg = store.registration
+    total = store.count(idxs)
+    if total == 0:
+        return 0, 0, []
+    d_out = C.c_void_p()
+    check(reg._lib.ndt_device_alloc(reg.ctx, total * 16, C.byref(d_out)), reg.ctx)
+    try:
+        n = store.build_into(d_out.value, total, [poses[i] for i in idxs], idxs, leaf)
+    except Exception:
+        reg._lib.ndt_device_free(reg.ctx, d_out)
+        raise
+    return d_out.value, n, [d_out.value]
+
+
 def refine_loop(keyframes, poses, loop_idx: int, curr_idx: int, search_num: int = 25, leaf: float = 0.5,
                 score_threshold: float = 0.3, device: int = 0, resolution: float = 1.0, literal_root: bool = False,
-                return_clouds: bool = False) -> dict:
+                return_clouds: bool = False, store=None) -> dict:
     """PGO::ICPRefine (pgo_node.cpp:404-483) for one loop candidate, without ROS or GTSAM.
 
     keyframes: list of (N, 4) x,y,z,intensity clouds in their sensor frames; poses: per keyframe (x, y, z, roll, pitch,
@@ -203,21 +220,31 @@ def refine_loop(keyframes, poses, loop_idx: int, curr_idx: int, search_num: int 
 
     literal_root: the reference's LoopFindNearKeyframesCloud never reads its `key` argument (it stacks root_idx + i, and
     :425 passes the loop keyframe as root), so its source cloud is the loop keyframe itself; True reproduces that.
+
+    store: a KeyframeMap that holds the keyframes on the device.  Both submaps are then built from it (one launch each
+    plus the VoxelGrid, no upload per loop) and ICP runs on the store's context, whose resolution, target and source it
+    sets; `keyframes` may be None and `device` is the store's.  The result is the same, bit for bit.
     """
-    n_kf = len(keyframes)
+    n_kf = len(keyframes) if store is None else len(store)
     if not (0 <= loop_idx < n_kf and 0 <= curr_idx < n_kf) or len(poses) != n_kf:
         raise ValueError("loop_idx / curr_idx out of range, or poses do not match keyframes")
     src_key = loop_idx if literal_root else curr_idx
     tgt_idx = [i for i in range(loop_idx - search_num, loop_idx + search_num + 1) if 0 <= i < n_kf]
-    icp = IterativeClosestPoint(device)
+    icp = IterativeClosestPoint(device, None if store is None else store.registration)
     reg = icp.registration
     to_free = []
     try:
         reg.setResolution(resolution)
-        d_src, n_src, f1 = _submap_device(reg, keyframes, poses, [src_key], leaf)
-        to_free += f1
-        d_tgt, n_tgt, f2 = _submap_device(reg, keyframes, poses, tgt_idx, leaf)
-        to_free += f2
+        if store is None:
+            d_src, n_src, f1 = _submap_device(reg, keyframes, poses, [src_key], leaf)
+            to_free += f1
+            d_tgt, n_tgt, f2 = _submap_device(reg, keyframes, poses, tgt_idx, leaf)
+            to_free += f2
+        else:
+            d_src, n_src, f1 = _submap_store(store, poses, [src_key], leaf)
+            to_free += f1
+            d_tgt, n_tgt, f2 = _submap_store(store, poses, tgt_idx, leaf)
+            to_free += f2
         out = {"n_source": n_src, "n_target": n_tgt}
         if return_clouds:
             for name, d, n in (("source_cloud", d_src, n_src), ("target_cloud", d_tgt, n_tgt)):

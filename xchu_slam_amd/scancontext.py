@@ -20,6 +20,7 @@ import numpy as np
 
 from ._ctxobj import _CtxObject
 from ._lib import ScParams, ScResult, check
+from .globalmap import KeyframeMap
 from .icp import refine_loop
 from .isc import detect_loops_isc
 from .ndt import NormalDistributionsTransform, _dp, _fp, as_points
@@ -175,7 +176,7 @@ def detect_loops(keyframes=None, tree_making_period: int = 1, device: int = 0, r
 
 
 def close_loops(keyframes, poses, max_pair_dist: float = 20.0, detect_args: dict | None = None, loop_method: int = 1,
-                **refine_args):
+                store=None, **refine_args):
     """pgo_node's loop-closure path for a whole replay: detect_loops, PerformSCLoopClosure's gate (pgo_node.cpp:351-362:
     the planar distance between the two keyframe poses must not exceed 20 m), then refine_loop (PGO::ICPRefine) for each
     surviving pair.  keyframes: (N, 4) x,y,z,intensity clouds; poses: per keyframe (x, y, z, roll, pitch, yaw).
@@ -190,10 +191,26 @@ def close_loops(keyframes, poses, max_pair_dist: float = 20.0, detect_args: dict
     **refine_args: every other keyword goes to refine_loop unchanged — search_num, leaf, score_threshold, device,
         resolution, literal_root.
 
+    store: a KeyframeMap holding the keyframes on the device, or True to build one from `keyframes` once for this call
+    (on refine_args' device): every refine_loop then builds its submaps from the resident keyframes instead of uploading
+    them again per loop, with the same results.  With a KeyframeMap given, `keyframes` may be None: the detector then
+    reads the clouds back from the store.
+
     Returns (accepted, rejected): accepted = [(loop_idx, curr_idx, transform, score)], rejected =
     [(loop_idx, curr_idx, reason)] with reason "pair_distance" or "icp"."""
+    if store is True:
+        with KeyframeMap(refine_args.get("device", 0)) as built:
+            for k in keyframes:
+                built.add(k)
+            return close_loops(keyframes, poses, max_pair_dist, detect_args, loop_method, built, **refine_args)
+    if store is not None and keyframes is None:
+        keyframes = [store.keyframe(i) for i in range(len(store))]
     if len(poses) != len(keyframes):
         raise ValueError("poses do not match keyframes")
+    if store is not None:
+        if len(store) != len(keyframes):
+            raise ValueError("the store does not match keyframes")
+        refine_args = dict(refine_args, store=store)
     if loop_method == 1:
         records = detect_loops([np.asarray(k)[:, :3] for k in keyframes], **(detect_args or {}))
     elif loop_method == 2:
