@@ -53,13 +53,42 @@ class Target:
         self.tree = cKDTree(self.pts.astype(np.float64)) if len(self.pts) else None
 
 
-def correspondences(X, tgt: Target, k: int = 4):
+def nearest_bruteforce(X, P, chunk_pairs: int = 1 << 22):
+    """Nearest point of P for every query of X over every pair (no tree, no candidate list): the f32 L2_Simple value of
+    each pair, in chunks of queries.  Returns (the lowest index of P at the minimum, the minimum as f32, the number of
+    points of P at the minimum).  Exact under any number of ties, which the k-nearest re-ranking of `correspondences`
+    is not: k candidates at one distance can crowd the lowest index out of the list."""
+    X = np.ascontiguousarray(np.asarray(X, F32)[:, :3])
+    P = np.ascontiguousarray(np.asarray(P, F32)[:, :3])
+    n, m = len(X), len(P)
+    if m == 0 or n == 0:
+        return np.full(n, -1, np.int64), np.full(n, np.inf, F32), np.zeros(n, np.int64)
+    idx = np.empty(n, np.int64)
+    best = np.empty(n, F32)
+    count = np.empty(n, np.int64)
+    rows = max(1, chunk_pairs // m)
+    for s in range(0, n, rows):
+        d2 = l2_simple_f32(P[None, :, :], X[s:s + rows, None, :])
+        b = d2.min(1)
+        at = d2 == b[:, None]
+        idx[s:s + rows] = at.argmax(1)  # the first True: the lowest index
+        best[s:s + rows] = b
+        count[s:s + rows] = at.sum(1)
+    return idx, best, count
+
+
+def correspondences(X, tgt: Target, k: int = 4, exact: bool = False):
     """Nearest target point of every query: the tree's k nearest re-ranked by the f32 L2_Simple value, equal values to
-    the lowest target index.  Returns (index, d2 as f32, queries with two candidates at an equal f32 distance)."""
+    the lowest target index.  Returns (index, d2 as f32, queries with two candidates at an equal f32 distance).
+    exact: every pair instead (nearest_bruteforce); the flags are then the queries with two or more target points at
+    the minimum."""
     X = np.asarray(X, F32)
     n, m = len(X), len(tgt.pts)
     if m == 0 or n == 0:
         return np.full(n, -1, np.int64), np.full(n, np.inf, F32), np.zeros(n, bool)
+    if exact:
+        idx, best, count = nearest_bruteforce(X, tgt.pts)
+        return idx, best, count > 1
     k = min(k, m)
     _, ii = tgt.tree.query(X.astype(np.float64), k=k, workers=WORKERS)
     ii = ii.reshape(n, k)
@@ -74,25 +103,28 @@ def correspondences(X, tgt: Target, k: int = 4):
     return idx, best.astype(F32), ties
 
 
-def umeyama(P, Q):
-    """Rigid transform P -> Q without scale (TransformationEstimationSVD / Eigen::umeyama), two-pass f64, as f32 4x4."""
-    P = np.asarray(P, np.float64)
-    Q = np.asarray(Q, np.float64)
+def umeyama(P, Q, dtype=np.float64):
+    """Rigid transform P -> Q without scale (TransformationEstimationSVD / Eigen::umeyama), two-pass f64, as f32 4x4.
+    dtype=np.longdouble evaluates the means, the cross-covariance and the translation in extended precision (the SVD
+    stays LAPACK's f64 one): the yardstick for how much of `final` is the estimate's own rounding."""
+    P = np.asarray(P, dtype)
+    Q = np.asarray(Q, dtype)
     pm, qm = P.mean(0), Q.mean(0)
     sigma = (Q - qm).T @ (P - pm) / len(P)
-    U, _, Vt = np.linalg.svd(sigma)
+    U, _, Vt = np.linalg.svd(sigma.astype(np.float64))
     s = -1.0 if np.linalg.det(U) * np.linalg.det(Vt) < 0 else 1.0
-    R = U @ np.diag([1.0, 1.0, s]) @ Vt
-    T = np.eye(4)
+    R = (U @ np.diag([1.0, 1.0, s]) @ Vt).astype(dtype)
+    T = np.eye(4, dtype=dtype)
     T[:3, :3] = R
     T[:3, 3] = qm - R @ pm
     return T.astype(F32)
 
 
 def icp(source, target, guess=None, max_corr_dist=float(np.sqrt(DBL_MAX)), max_iter=10, trans_eps=0.0, fit_eps=0.0,
-        min_pairs=3, k=4, tgt: Target | None = None):
+        min_pairs=3, k=4, tgt: Target | None = None, exact: bool = False, estimate_dtype=np.float64):
     """align(guess).  Returns final (f32 4x4), converged, state, iterations, mse, pairs and the per-iteration history
-    (incremental T, pairs, mse, state, and the iteration's matched index (-1 rejected) / d2 / tie flags)."""
+    (incremental T, pairs, mse, state, and the iteration's matched index (-1 rejected) / d2 / tie flags).
+    exact: correspondences over every pair (exact under ties) instead of the tree's k nearest; estimate_dtype: umeyama's."""
     tgt = Target(target) if tgt is None else tgt
     guess = np.eye(4, dtype=F32) if guess is None else np.asarray(guess, F32)
     final = guess.copy()
@@ -105,7 +137,7 @@ def icp(source, target, guess=None, max_corr_dist=float(np.sqrt(DBL_MAX)), max_i
     hist = []
     converged, state, mse, pairs = False, NOT_CONVERGED, 0.0, 0
     while True:
-        idx, d2, ties = correspondences(X, tgt, k)
+        idx, d2, ties = correspondences(X, tgt, k, exact)
         keep = (idx >= 0) & (d2.astype(np.float64) <= max_corr2)
         pairs = int(keep.sum())
         mse = float(d2[keep].astype(np.float64).sum() / pairs) if pairs else 0.0
@@ -115,7 +147,7 @@ def icp(source, target, guess=None, max_corr_dist=float(np.sqrt(DBL_MAX)), max_i
             state, converged = NO_CORRESPONDENCES, False
             rec["state"] = state
             break
-        T = umeyama(X[keep], tgt.pts[idx[keep]])
+        T = umeyama(X[keep], tgt.pts[idx[keep]], estimate_dtype)
         rec["T"] = T
         X = transform_f32(T, X)
         final = mat4_mul_f32(T, final)
