@@ -230,6 +230,85 @@ ndt_status ndt_icp_correspondences(ndt_ctx* ctx, int* index, float* d2, size_t c
 /* After ndt_icp_align, ndt_get_output returns the source transformed by the ICP's final transformation, and
  * ndt_fitness_score with T = NULL scores that transformation (the last align of either kind). */
 
+/* ---- Generalized-ICP: pclomp::GeneralizedIterativeClosestPoint (xchu_mapping/include/pclomp/gicp_omp.h,
+ * gicp_omp_impl.hpp), the reference library's third registration method — a pcl::Registration operator on the same ctx
+ * as ndt_icp_align.  Semantics are the restatement of DESIGN.md (GICP; parity unpinned): per point of either cloud the
+ * covariance of its k nearest neighbours (ascending (d^2, index), the point included), regularised to singular values
+ * (1, 1, gicp_epsilon); per outer iteration the exact nearest target point of every source point moved by guess and then
+ * by the running transformation, pairs with d^2 < max_corr_dist^2 kept (strict), M_i = (R C1_i R^T + C2_j)^-1; fewer than
+ * 4 pairs = NDT_GICP_NO_CORRESPONDENCES; otherwise sum res^T M res / m is minimised over (x, y, z, roll, pitch, yaw) by the
+ * project's BFGS with Fletcher's line search (PCL's bfgs.h is not part of the reference tree: documented deviation), and
+ * the iteration ends the align when delta < 1 or max_iter is reached.  PCL's treatment of the guess is kept: the
+ * objective and the final transformation use R(x) R_guess and t_guess + x_t, the search the full product.
+ * k_correspondences above 32, or a cloud with fewer than k points, is NDT_EINVAL (the reference logs and reads an empty
+ * vector).  Caller-supplied covariances (setSourceCovariances / setTargetCovariances) are not supported. */
+typedef enum {
+    NDT_GICP_NOT_CONVERGED = 0,
+    NDT_GICP_ITERATIONS = 1,         /* outer iterations >= max_iter                                                 */
+    NDT_GICP_DELTA = 2,              /* max |prev - cur| scaled by 1/rot_eps (3x3 corner) or 1/trans_eps is below 1   */
+    NDT_GICP_NO_CORRESPONDENCES = 3, /* fewer than 4 pairs: converged = 0, final from the transformation before        */
+    NDT_GICP_SOLVER_FAILED = 4       /* the minimiser ran out of evaluations or bracketing steps: as above            */
+} ndt_gicp_state;
+
+/* ndt_gicp_record::min_status */
+typedef enum {
+    NDT_GICP_MIN_RUNNING = 0,
+    NDT_GICP_MIN_SUCCESS = 1,        /* |g| < 1e-2                                                                   */
+    NDT_GICP_MIN_NO_PROGRESS = 2,    /* no descent direction, or a line search stopped by round-off                  */
+    NDT_GICP_MIN_MAX_INNER = 3,      /* max_inner_iter line searches done                                            */
+    NDT_GICP_MIN_FAILED = 4
+} ndt_gicp_min_status;
+
+typedef struct {
+    double max_corr_dist;            /* setMaxCorrespondenceDistance     default 5                                   */
+    int max_iter;                    /* setMaximumIterations             default 200                                 */
+    double trans_eps;                /* setTransformationEpsilon         default 5e-4                                */
+    double rot_eps;                  /* setRotationEpsilon               default 2e-3                                */
+    int k_correspondences;           /* setCorrespondenceRandomness      default 20, at most 32                      */
+    double gicp_epsilon;             /* smallest singular value of a regularised covariance, default 1e-3            */
+    int max_inner_iter;              /* setMaximumOptimizerIterations    default 20                                  */
+} ndt_gicp_params;
+
+typedef struct {
+    float final_tf[16];              /* getFinalTransformation(), column-major                                       */
+    int converged;                   /* hasConverged()                                                               */
+    int state;                       /* ndt_gicp_state                                                               */
+    int nr_iterations;               /* outer iterations completed                                                   */
+    double f;                        /* the objective at the end of the last inner solve                             */
+    long long n_pairs;               /* pairs of the last outer iteration                                            */
+    long long n_evals;               /* objective evaluations of the whole align                                     */
+} ndt_gicp_result;
+
+/* One outer iteration: transformation_ after it (before it for an iteration that ended the align unconverged). */
+typedef struct {
+    float T[16];
+    long long n_pairs;
+    double f;
+    int inner_iterations;
+    int n_evals;
+    int min_status;                  /* ndt_gicp_min_status                                                          */
+    double delta;
+    int state;                       /* ndt_gicp_state                                                               */
+} ndt_gicp_record;
+
+ndt_status ndt_gicp_default_params(ndt_gicp_params* out);
+/* gicp.align(output, guess) over the ctx's target and source.  prm NULL = the defaults, guess NULL = identity.
+ * Synchronous.  Afterwards ndt_get_output and ndt_fitness_score(T = NULL) refer to this align (the last align of any
+ * kind).  Covariances are kept until their cloud, k_correspondences or gicp_epsilon changes. */
+ndt_status ndt_gicp_align(ndt_ctx* ctx, const ndt_gicp_params* prm, const float guess[16], ndt_gicp_result* out);
+/* Per-outer-iteration trace of the last GICP align. */
+ndt_status ndt_gicp_history(ndt_ctx* ctx, ndt_gicp_record* out, int cap, int* n_out);
+/* Test hooks.  Covariances of the target (which = 0) or source (1) under prm (NULL = defaults), 9 f64 per point; raw != 0:
+ * the covariances before the SVD.  *n_out = the cloud's size. */
+ndt_status ndt_gicp_covariances(ndt_ctx* ctx, const ndt_gicp_params* prm, int which, int raw, double* out, size_t cap, size_t* n_out);
+/* The last outer iteration's pairs: matched target index (-1 rejected), d^2, and M_i (9 f64, rows; rejected: stale). */
+/* Both hooks below are NDT_EINVAL once the source has been replaced since that align. */
+ndt_status ndt_gicp_correspondences(ndt_ctx* ctx, int* index, float* d2, double* M9, size_t cap, size_t* n_out);
+/* The objective of the last outer iteration's pairs and its gradient at x, one launch. */
+ndt_status ndt_gicp_evaluate(ndt_ctx* ctx, const double x[6], double* f, double g[6]);
+/* Profiling hook (tools/gicp_profile.py): kernel launches and host round trips of the last GICP align. */
+ndt_status ndt_gicp_run_stats(ndt_ctx* ctx, int* launches, int* rounds);
+
 /* ---- Scan Context: SCManager (xchu_mapping/include/scancontext/Scancontext.{h,cpp}), pgo_node's default loop detector
  * (loop_method 1: makeAndSaveScancontextAndKeys per keyframe at pgo_node.cpp:236, detectLoopClosureID at :344).  The
  * descriptors (20 rings x 60 sectors over 80 m, lidar height 2.0), their ring keys, sector keys and column norms stay in

@@ -5,6 +5,7 @@ host mirror of the pclomp::NormalDistributionsTransform API.  See DESIGN.md.
 """
 from .odom import LidarOdom  # noqa: F401
 from .icp import IterativeClosestPoint, refine_loop  # noqa: F401
+from .gicp import GeneralizedIterativeClosestPoint  # noqa: F401
 from .scancontext import SCManager, close_loops, detect_loops  # noqa: F401
 from .isc import ISCGeneration, detect_loops_isc  # noqa: F401
 from .posegraph import PoseGraph, loop_measurement, optimize_loops  # noqa: F401

@@ -113,6 +113,43 @@ class IcpRecord(C.Structure):
     ]
 
 
+class GicpParams(C.Structure):
+    _fields_ = [
+        ("max_corr_dist", C.c_double),
+        ("max_iter", C.c_int),
+        ("trans_eps", C.c_double),
+        ("rot_eps", C.c_double),
+        ("k_correspondences", C.c_int),
+        ("gicp_epsilon", C.c_double),
+        ("max_inner_iter", C.c_int),
+    ]
+
+
+class GicpResult(C.Structure):
+    _fields_ = [
+        ("final_tf", C.c_float * 16),
+        ("converged", C.c_int),
+        ("state", C.c_int),
+        ("nr_iterations", C.c_int),
+        ("f", C.c_double),
+        ("n_pairs", C.c_longlong),
+        ("n_evals", C.c_longlong),
+    ]
+
+
+class GicpRecord(C.Structure):
+    _fields_ = [
+        ("T", C.c_float * 16),
+        ("n_pairs", C.c_longlong),
+        ("f", C.c_double),
+        ("inner_iterations", C.c_int),
+        ("n_evals", C.c_int),
+        ("min_status", C.c_int),
+        ("delta", C.c_double),
+        ("state", C.c_int),
+    ]
+
+
 class ScParams(C.Structure):
     _fields_ = [
         ("dist_thres", C.c_double),
@@ -198,6 +235,8 @@ class PgoRecord(C.Structure):
 
 # ndt_icp_state
 ICP_NOT_CONVERGED, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
+# ndt_gicp_state
+GICP_NOT_CONVERGED, GICP_ITERATIONS, GICP_DELTA, GICP_NO_CORRESPONDENCES, GICP_SOLVER_FAILED = range(5)
 
 
 class OdomParams(C.Structure):
@@ -282,6 +321,14 @@ SIGNATURES = {
     "ndt_icp_align": (C.c_int, [_P, C.POINTER(IcpParams), _FP, C.POINTER(IcpResult)]),
     "ndt_icp_history": (C.c_int, [_P, C.POINTER(IcpRecord), C.c_int, C.POINTER(C.c_int)]),
     "ndt_icp_correspondences": (C.c_int, [_P, C.POINTER(C.c_int), _FP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ndt_gicp_default_params": (C.c_int, [C.POINTER(GicpParams)]),
+    "ndt_gicp_align": (C.c_int, [_P, C.POINTER(GicpParams), _FP, C.POINTER(GicpResult)]),
+    "ndt_gicp_history": (C.c_int, [_P, C.POINTER(GicpRecord), C.c_int, C.POINTER(C.c_int)]),
+    "ndt_gicp_covariances": (C.c_int, [_P, C.POINTER(GicpParams), C.c_int, C.c_int, C.POINTER(C.c_double), C.c_size_t,
+                                       C.POINTER(C.c_size_t)]),
+    "ndt_gicp_correspondences": (C.c_int, [_P, C.POINTER(C.c_int), _FP, C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ndt_gicp_evaluate": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ndt_gicp_run_stats": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ndt_sc_default_params": (C.c_int, [C.POINTER(ScParams)]),
     "ndt_sc_create": (C.c_int, [_P, C.POINTER(ScParams), C.POINTER(_P)]),
     "ndt_sc_destroy": (None, [_P]),

@@ -647,6 +647,7 @@ ndt_status ndt_set_source(ndt_ctx* c, const float* xyz, size_t n, size_t stride_
     if (c->source.p != old) invalidate_graph(c);  // a new size alone keeps the chains (geom_points)
     c->N = (int)n;
     c->has_source = true;
+    ++c->src_gen;
     c->have_result = false;
     return NDT_OK;
 }
@@ -667,6 +668,7 @@ ndt_status ndt_set_source_device(ndt_ctx* c, const float* d_xyz4, size_t n) {
     c->N = (int)n;
     if (!NDT_DEFER_SOURCE) TRY(flush_source(c));
     c->has_source = true;
+    ++c->src_gen;
     c->have_result = false;
     return NDT_OK;
 }

@@ -243,6 +243,7 @@ void ndt_destroy(ndt_ctx* c) {
     for (hipStream_t st : {c->stream.get(), c->lanes.fit_stream.get(), c->lanes.ins_stream.get()}) if (st) (void)hipStreamSynchronize(st);
     invalidate_graph(c);
     c->icp.graph.reset();
+    c->gicp.graph.reset();
     delete c;
 }
 

@@ -228,12 +228,43 @@ struct IcpRun {
     DevBuf<IcpRecordDev> d_hist;
     Pinned<IcpState[]> h_state;
     bool used = false;                  // the fit index of this ctx carries the points' original indices from now on
-    bool last = false;                  // the result have_result speaks of is the ICP's (final_tf), not the NDT align's
+    bool last = false;                  // the result have_result speaks of is the ICP's or GICP's (final_tf), not the NDT align's
     float final_tf[16] = {0};
     int n = 0;                          // source points of the last ICP align
     std::vector<IcpRecordDev> hist;
     GraphExec graph;
     long long graph_key[12] = {0};
+};
+
+// host_gicp.hip — Generalized-ICP (ndt_gicp_align): the source's own neighbour index, the per-point covariances of both
+// clouds (9 f64 each, kept until the cloud, k or epsilon changes), the last outer iteration's per-point pair data, the
+// evaluation partials and the two tickets, the device state and history with the pinned state copies ([0] read back,
+// [1] the state uploaded; the three made together), and the last run's record.
+struct GicpRun {
+    struct Cov {
+        DevBuf<double> buf;
+        bool valid = false;
+        unsigned long long gen = 0;
+        int k = 0;
+        double eps = 0.0;
+    };
+    NNIndex src_ix;
+    Cov cov_src, cov_tgt;
+    DevBuf<double> raw;                 // test hook: the covariances before the SVD
+    DevBuf<int> match;
+    DevBuf<float> d2;
+    DevBuf<float4> qt, gp;              // matched target point, guess * p
+    DevBuf<double> M, part;
+    DevBuf<unsigned> ticket;
+    DevBuf<GicpState> d_state;
+    DevBuf<GicpRecordDev> d_hist;
+    Pinned<GicpState[]> h_state;
+    int n = 0;                          // source points of the last GICP align
+    unsigned long long src_gen = 0;     // the source that align ran over (the hooks refuse another)
+    GraphExec graph;                    // one round of launches and the state read-back
+    long long graph_key[16] = {0};
+    int launches = 0, rounds = 0;       // of the last align
+    std::vector<GicpRecordDev> hist;
 };
 
 // Member order is part of the design: members are released in reverse order of declaration (delete c, the last step of
@@ -314,6 +345,7 @@ struct ndt_ctx {
     DevBuf<float4> source;
     int N = 0;
     bool has_source = false;
+    unsigned long long src_gen = 0;     // one per setInputSource (GICP's source covariances)
     const float4* src_pend = nullptr;   // ndt_set_source_device's copy, deferred to the next align (its k_align_init) or flush_source
     // source in target-cell order for the passes of an align (k_src_keys): the cloud the pass kernels read
     DevBuf<float4> source_ord;
@@ -348,6 +380,7 @@ struct ndt_ctx {
     PassProf prof;
     bool have_result = false;
     IcpRun icp;
+    GicpRun gicp;
     // graph cache: a few captured chains (different slot counts / buffers), round-robin replacement
     static constexpr int kGraphKey = 23;
     static constexpr int kGraphCache = 64;

@@ -6,6 +6,7 @@
 #include "ndt_types.h"
 #include "ndt_linalg.h"
 #include "ndt_icp.h"
+#include "ndt_gicp.h"
 #include "ndt_sc.h"
 #include "ndt_isc.h"
 #include "ndt_pgo.h"
@@ -41,6 +42,13 @@ __global__ void k_fit_gather(const float4*, const int*, const int*, const int*, 
                              int*, int*, int*);
 __global__ void k_icp_pass(float4*, int, IcpState*, const GridHeader*, const int*, const int*, const float4*, const int*, int*, float*,
                            double*, unsigned*, IcpRecordDev*);
+template <int C>
+__global__ void k_gicp_cov(const float4*, int, int, double, const GridHeader*, const int*, const int*, const float4*, const int*, double*,
+                           double*);
+__global__ void k_gicp_pairs(const float4*, int, GicpState*, const GridHeader*, const int*, const int*, const float4*, const int*,
+                             const double*, const double*, int*, float*, float4*, float4*, double*, unsigned*, GicpRecordDev*);
+__global__ void k_gicp_eval(const float4*, int, GicpState*, const int*, const float4*, const float4*, const double*, double*, unsigned*,
+                            GicpRecordDev*);
 __global__ void k_sc_make(const float4*, int, unsigned*);
 __global__ void k_sc_finalize(const unsigned*, ScDb, int);
 __global__ void k_sc_detect(ScDb, const int*, const int*, int, int, ScDetectArgs, ndt_sc_result*);

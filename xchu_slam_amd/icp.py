@@ -209,7 +209,7 @@ def _submap_store(store, poses, idxs, leaf: float):
 
 def refine_loop(keyframes, poses, loop_idx: int, curr_idx: int, search_num: int = 25, leaf: float = 0.5,
                 score_threshold: float = 0.3, device: int = 0, resolution: float = 1.0, literal_root: bool = False,
-                return_clouds: bool = False, store=None) -> dict:
+                return_clouds: bool = False, store=None, method: str = "icp", gicp_args: dict | None = None) -> dict:
     """PGO::ICPRefine (pgo_node.cpp:404-483) for one loop candidate, without ROS or GTSAM.
 
     keyframes: list of (N, 4) x,y,z,intensity clouds in their sensor frames; poses: per keyframe (x, y, z, roll, pitch,
@@ -224,13 +224,27 @@ def refine_loop(keyframes, poses, loop_idx: int, curr_idx: int, search_num: int 
     store: a KeyframeMap that holds the keyframes on the device.  Both submaps are then built from it (one launch each
     plus the VoxelGrid, no upload per loop) and ICP runs on the store's context, whose resolution, target and source it
     sets; `keyframes` may be None and `device` is the store's.  The result is the same, bit for bit.
+
+    method: "icp" (the reference's refinement, the default) or "gicp": GeneralizedIterativeClosestPoint in ICP's place with
+    its own defaults (5 m, 200 iterations, epsilons 5e-4 / 2e-3, k 20), overridden by gicp_args (ndt_gicp_params' field
+    names: max_corr_dist, max_iter, trans_eps, rot_eps, k_correspondences, gicp_epsilon, max_inner_iter); the same
+    acceptance rule.
     """
+    if method not in ("icp", "gicp"):
+        raise ValueError("method must be 'icp' or 'gicp'")
+    if gicp_args and method != "gicp":
+        raise ValueError("gicp_args needs method='gicp'")
     n_kf = len(keyframes) if store is None else len(store)
     if not (0 <= loop_idx < n_kf and 0 <= curr_idx < n_kf) or len(poses) != n_kf:
         raise ValueError("loop_idx / curr_idx out of range, or poses do not match keyframes")
     src_key = loop_idx if literal_root else curr_idx
     tgt_idx = [i for i in range(loop_idx - search_num, loop_idx + search_num + 1) if 0 <= i < n_kf]
-    icp = IterativeClosestPoint(device, None if store is None else store.registration)
+    if method == "gicp":
+        from .gicp import GeneralizedIterativeClosestPoint
+        icp = GeneralizedIterativeClosestPoint(device, None if store is None else store.registration)
+        icp._with_overrides(icp._params, gicp_args or {})
+    else:
+        icp = IterativeClosestPoint(device, None if store is None else store.registration)
     reg = icp.registration
     to_free = []
     try:
@@ -257,11 +271,12 @@ def refine_loop(keyframes, poses, loop_idx: int, curr_idx: int, search_num: int 
             out.update(transform=np.eye(4, dtype=np.float32), score=float(np.finfo(np.float64).max), converged=False,
                        accepted=False, iterations=0, state=_lib.ICP_NOT_CONVERGED)
             return out
-        icp.setMaxCorrespondenceDistance(150)
-        icp.setMaximumIterations(100)
-        icp.setTransformationEpsilon(1e-6)
-        icp.setEuclideanFitnessEpsilon(1e-6)
-        icp.setRANSACIterations(0)
+        if method == "icp":
+            icp.setMaxCorrespondenceDistance(150)
+            icp.setMaximumIterations(100)
+            icp.setTransformationEpsilon(1e-6)
+            icp.setEuclideanFitnessEpsilon(1e-6)
+            icp.setRANSACIterations(0)
         icp.setInputSourceDevice(d_src, n_src)
         icp.setInputTargetDevice(d_tgt, n_tgt)
         icp.align(want_output=False)
