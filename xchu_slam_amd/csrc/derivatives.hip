@@ -204,6 +204,15 @@ template <> struct PairSlot<2> {
 #ifndef NDT_OWN_FIRST
 #define NDT_OWN_FIRST 1
 #endif
+// A/B switches of the leading-tail kernel's stretch between the control step and the body (profiles/r08_pass_header/AB.md):
+// 1 = partials_pending set in the state word workgroup 0 writes out (0: in LDS, behind a barrier of its own); 1 = the grid
+// header's lines touched at kernel start
+#ifndef NDT_LEAD_FLAG_PATCH
+#define NDT_LEAD_FLAG_PATCH 1
+#endif
+#ifndef NDT_LEAD_WARM
+#define NDT_LEAD_WARM 1
+#endif
 // a wave-uniform double moved to SGPRs (its two halves read from the first active lane)
 __device__ __forceinline__ double uniform_d(double x) {
     const long long b = __double_as_longlong(x);
@@ -690,6 +699,15 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
         if (t < kExpTabLen) s_exp[t] = __longlong_as_double((long long)ew);
         if (t < kWords) lw[t] = a;
         if (t + B < kWords) lw[t + B] = b;
+        if (NDT_LEAD_WARM) {
+            // one word of each of the grid header's three 64-byte lines the body reads (none of them a word it reads):
+            // the lines are in the scalar cache when the body's header loads come, behind the control step, where they
+            // are three dependent round trips (dense / hash dispatch, halo sizes, the rest)
+            const unsigned* w = reinterpret_cast<const unsigned*>(hdr);
+            const unsigned touch = w[offsetof(GridHeader, min_b) / 4 + 3] ^ w[offsetof(GridHeader, inv_leaf) / 4 + 3] ^
+                                   w[offsetof(GridHeader, n_points) / 4];
+            asm volatile("" ::"s"(touch));
+        }
     }
     lds_barrier();
     // profiling: this kernel's start is the start of its body's pass and the end of the pass whose partials it consumes
@@ -717,7 +735,7 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
         t_reduced = __builtin_amdgcn_s_memrealtime();
 #endif
         tail_control<NW>(s_st, red, hist, blockIdx.x == 0 ? hist_cap : 0, nullptr);
-        if (threadIdx.x == 0) s_st.partials_pending = 0;
+        if (!NDT_LEAD_FLAG_PATCH && threadIdx.x == 0) s_st.partials_pending = 0;
         lds_barrier();
     }
 #ifdef NDT_BODY_STAMPS
@@ -733,12 +751,24 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
         if (consumed && k - 1 >= 0 && k - 1 < kMaxHistory) ts[kTsStride * (k - 1) + 1] = t_start;
         if (body && k < kMaxHistory) ts[kTsStride * k] = t_start;
     }
-    if (threadIdx.x == 0 && body) s_st.partials_pending = 1;
-    lds_barrier();
+    // partials_pending of the state this kernel leaves (1: its body's partials are to be consumed).  No thread of this
+    // kernel reads it again, so workgroup 0 sets it in the word it writes out; set in LDS it took a workgroup barrier of its
+    // own in every workgroup, between the control step and the body (C2 17.83 -> 17.70 us per pass, profiles/r08_pass_header)
+    if (!NDT_LEAD_FLAG_PATCH) {
+        if (threadIdx.x == 0 && body) s_st.partials_pending = 1;
+        lds_barrier();
+    }
     if (blockIdx.x == 0) {
         const unsigned long long* lw = reinterpret_cast<const unsigned long long*>(&s_st);
         unsigned long long* gw = reinterpret_cast<unsigned long long*>(st_out);
-        for (int k = threadIdx.x; k < kWords; k += B) gw[k] = lw[k];
+        constexpr int kFlagWord = offsetof(AlignState, partials_pending) / 8;
+        constexpr int kFlagShift = (offsetof(AlignState, partials_pending) % 8) * 8;
+        for (int k = threadIdx.x; k < kWords; k += B) {
+            unsigned long long w = lw[k];
+            if (NDT_LEAD_FLAG_PATCH && k == kFlagWord)
+                w = (w & ~(0xffffffffull << kFlagShift)) | ((unsigned long long)(body ? 1u : 0u) << kFlagShift);
+            gw[k] = w;
+        }
     }
     if (!body) return;
     __shared__ double redw[NW * kNumAcc];
