@@ -72,10 +72,10 @@ def lattice_scene(seed=0, nx=12, ny=12, nz=6, n_dup=200, spacing=1):
     exact in f32; at resolution 1.0 every point lies on a cell face).  Queries: the cell centres (8 candidates in 8
     cells), the midpoints of the x edges (2 candidates), and 288 lattice points, the repeated ones among them (d2 = 0,
     the tie inside one cell).  Returns (target, queries, kinds) with kinds 0 / 1 / 2 per query.
-    spacing=1: the 8 candidates of a centre sit in 8 cells that 8 different lanes of the team scan, so only arg_team
+    spacing=1: the 8 candidates of a centre sit in 8 cells that 8 different lanes of the team scan, so only NnArg::team
     orders them.  spacing=2: the centres are cell corners (face distance 0) with candidates at d2 = 3 in the cells at
     offsets (+-1, +-1, +-1); the radius-1 cube cannot conclude, and in both cubes two of the eight fall to one lane
-    (cells 2 and 18, 8 and 24 of the 27; 33 and 81, 43 and 91 of the 125), so arg_take's own tie branch orders them and
+    (cells 2 and 18, 8 and 24 of the 27; 33 and 81, 43 and 91 of the 125), so NnArg::take's own tie branch orders them and
     the second cube meets every candidate again."""
     rng = np.random.default_rng(seed)
     g = np.stack(np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nz), indexing="ij"), -1).reshape(-1, 3).astype(np.float64)

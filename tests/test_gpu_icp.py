@@ -93,6 +93,10 @@ def test_far_walk(scene):
     with make_icp(xa, pair.target, src, max_iter=1) as icp:
         icp.align(want_output=False)
         check_first_iteration(icp, ref)
+        # with the identity both kernels' queries are the source points themselves: getFitnessScore's minimum and the
+        # pass's argmin come out of one walk (in-grid cells, cells outside the grid, block shells) bit for bit
+        _, d_fit = icp.getFitnessScore(T=np.eye(4, dtype=np.float32), return_distances=True)
+        assert np.array_equal(d_fit.view(np.uint32), icp.correspondences()[1].view(np.uint32))
     # the same with pgo_node's 150 m: the 5 far points are searched (their d2 is reported) and rejected
     ref = R.icp(src, pair.target, tgt=scene["tgt"], max_iter=1, max_corr_dist=150.0)
     assert ref["history"][0]["pairs"] == len(src) - 5

@@ -1,5 +1,5 @@
-"""k_icp_pass at the edges tests/test_gpu_icp.py leaves unrun: ties (the `d == a.d` branch of arg_take, the (d, orig)
-order of arg_team, the index's fifth word), degenerate targets and queries on every side of the grid, inexact and
+"""k_icp_pass at the edges tests/test_gpu_icp.py leaves unrun: ties (the `v == d` branch of NnArg::take, the (d, orig)
+order of NnArg::team, the index's fifth word), degenerate targets and queries on every side of the grid, inexact and
 doubled index cells, sources past one trip of the grid-stride loop, the estimate's reflection and rank-deficient
 branches, ABS_MSE / REL_MSE on the device, and map-frame coordinates.
 
@@ -59,7 +59,7 @@ def run_one_exact(target, source, resolution=1.0):
 def test_ties_lattice(order, spacing):
     """Cell centres (8 candidates in 8 cells), edge midpoints (2), lattice points with repeated target points (d2 = 0,
     ties inside one cell, which the index's stable sort keeps in the caller's order): the winner is the lowest index in
-    the caller's order, whichever order that is.  Spacing 1 leaves every tie between cells to arg_team; spacing 2 puts
+    the caller's order, whichever order that is.  Spacing 1 leaves every tie between cells to NnArg::team; spacing 2 puts
     two candidates of a centre query into one lane's cells, in both cubes (icp_edge_scenes.lattice_scene)."""
     tgt, q, kinds = S.lattice_scene(spacing=spacing)
     census = S.tie_census(q, tgt, 1.0)

@@ -4,9 +4,9 @@
 //                  The walk of k_sor_knn (3x3x3 cube, ring 2, block shells, the same bound); every lane keeps the C
 //                  smallest 64-bit keys (d2 bits << 32 | original index) it saw, so the (d2, index) order rule and the
 //                  summation order both come out of the merge.  f64 mean and moments in that order, svd_jacobi, rebuild.
-//   k_gicp_pairs   one outer iteration's correspondences (:430-463): both transforms, the exact 1-NN walk of k_icp_pass
-//                  (ndt_nnwalk.h), the strict threshold, M_i = (R C1 R^T + C2)^-1; its last workgroup runs
-//                  gicp_after_pairs.
+//   k_gicp_pairs   one outer iteration's correspondences (:430-463): both transforms, the exact 1-NN walk with the
+//                  argmin tracker (ndt_nnwalk.h, as k_icp_pass), the strict threshold, M_i = (R C1 R^T + C2)^-1; its
+//                  last workgroup runs gicp_after_pairs.
 //   k_gicp_eval    the objective and its gradient (:344-377) at the state's trial transform: 13 f64 sums over the
 //                  matched points through a fixed tree, per-workgroup partials, the last workgroup sums them through
 //                  a fixed tree too and runs gicp_after_eval (the minimiser step, the next trial transform, the end of a solve).
@@ -18,13 +18,14 @@
 #include "ndt_linalg.h"
 #include "ndt_gicp.h"
 #include "ndt_nnwalk.h"
+#include "ndt_lastwg.h"
 #include "ndt_kernels.h"
 
 namespace ndt {
 
 namespace {
 
-static_assert(kGicpTeam == kIcpTeam, "k_gicp_pairs' teams are nn_walk's");
+static_assert(kGicpTeam == kNnTeam, "k_gicp_pairs' teams are nn_walk's");
 
 constexpr unsigned long long kNoKey = ~0ull;
 
@@ -67,7 +68,7 @@ __device__ __forceinline__ int gicp_team_sum(int v) {
 template <int C>
 __device__ __forceinline__ void take(TopKey<C>& top, const float4* __restrict__ ix_pts, const int* __restrict__ ix_idx, int j,
                                      const float q[3]) {
-    const float d = icp_l2(ix_pts[j], q);
+    const float d = nn_l2(ix_pts[j], q);
     const unsigned hi = __float_as_uint(d);
     if (hi > (unsigned)(top.v[C - 1] >> 32)) return;  // d2 >= 0: the bits order as the values
     top.insert(((unsigned long long)hi << 32) | (unsigned)ix_idx[j]);
@@ -226,8 +227,8 @@ __global__ __launch_bounds__(kGicpBlock) void k_gicp_pairs(const float4* __restr
         const float gz = ((G[2] * p.x + G[6] * p.y) + G[10] * p.z) + G[14];
         const float q[3] = {((T[0] * gx + T[4] * gy) + T[8] * gz) + T[12], ((T[1] * gx + T[5] * gy) + T[9] * gz) + T[13],
                             ((T[2] * gx + T[6] * gy) + T[10] * gz) + T[14]};
-        Arg a = {INFINITY, -1, INT_MAX};
-        if (!empty) nn_walk(q, t, h, db, nbk, cell, block_table, cell_off, fit_pts, fit_idx, a);
+        NnArg a = {INFINITY, -1, INT_MAX, fit_idx};
+        if (!empty) nn_walk(q, t, h, db, nbk, cell, block_table, cell_off, fit_pts, a);
         const bool keep = a.pos >= 0 && (double)a.d < corr2;  // strict, unlike ICP
         if (t == 0) {
             match[i] = keep ? a.orig : -1;
@@ -303,11 +304,9 @@ __global__ __launch_bounds__(kGicpBlock) void k_gicp_eval(const float4* __restri
 #pragma unroll
             for (int b = 0; b < 3; ++b) acc[4 + 3 * a + b] += gd[a] * tmp[b];
     }
-    // ---- a fixed tree: the wave's lanes, the waves in order, then the workgroups' partials (one per thread, the same tree)
+    // ---- a fixed tree: the wave's lanes, the waves in order, then the workgroups' partials (ndt_lastwg.h)
     constexpr int kWaves = kGicpBlock / 64;
     __shared__ double s_part[kWaves][kGicpSums];
-    __shared__ double s_tot[kGicpSums];
-    __shared__ int s_last;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < kGicpSums; ++k) {
@@ -315,44 +314,8 @@ __global__ __launch_bounds__(kGicpBlock) void k_gicp_eval(const float4* __restri
         for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
         if (lane == 0) s_part[wave][k] = v;
     }
-    __syncthreads();
-    const int nb = gridDim.x;
-    if (threadIdx.x < 64) {
-        if (threadIdx.x < kGicpSums) {
-            double v = s_part[0][threadIdx.x];
-            for (int w = 1; w < kWaves; ++w) v += s_part[w][threadIdx.x];
-            __hip_atomic_store(partials + (size_t)threadIdx.x * nb + blockIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // the partials are stored by lanes of wave 0 and drained before its lane 0 takes the ticket (k_icp_pass's hand-off)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (threadIdx.x == 0)
-            s_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)nb - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // s_part is reused
-    for (int k = 0; k < kGicpSums; ++k) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < nb; b += kGicpBlock)
-            v += __hip_atomic_load(partials + (size_t)k * nb + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-        if (lane == 0) s_part[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kGicpSums) {
-        double v = s_part[0][threadIdx.x];
-        for (int w = 1; w < kWaves; ++w) v += s_part[w][threadIdx.x];
-        s_tot[threadIdx.x] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        *ticket = 0u;  // re-armed for the next launch
-        double S[kGicpSums];
-        for (int k = 0; k < kGicpSums; ++k) S[k] = s_tot[k];
-        gicp_after_eval(st, hist, S);
-    }
+    double S[kGicpSums];
+    if (last_workgroup_sums<kGicpSums, kGicpBlock>(s_part, partials, ticket, S)) gicp_after_eval(st, hist, S);
 }
 
 }  // namespace ndt

@@ -28,24 +28,6 @@ static void launch_cov(ndt_ctx* c, const float4* pts, int n, const ndt_gicp_para
                            ix.hdr.p, ix.blk.p, ix.off.p, ix.pts.p, ix.idx.p, out, raw);
 }
 
-// the target's nearest-neighbour index with the points' original indices, built and visible to the main stream
-static ndt_status gicp_target_index(ndt_ctx* c) {
-    if (!c->icp.used) {
-        c->icp.used = true;
-        c->fit_valid = false;  // rebuilt behind the fit lane's queued queries (FIFO)
-    }
-    TRY(ensure_fit_index(c));
-    std::string msg;
-    const ndt_status st = c->lanes.fit_worker->take_error(&msg);  // the index build has been issued
-    if (st != NDT_OK) {
-        c->fit_valid = false;
-        c->lanes.fit_pending = false;
-        return fail(c, st, "GICP: nearest-neighbour index: " + msg);
-    }
-    HIPCHK(c, hipStreamWaitEvent(c->stream.get(), c->lanes.ev_fit_tgt.get(), 0));
-    return NDT_OK;
-}
-
 // Covariances of the target (which = 0) or the source (1), kept until that cloud, k or epsilon changes (the reference
 // resets them in setInputTarget / setInputSource).  raw: also the covariances before the SVD, always recomputed.
 static ndt_status gicp_covariances(ndt_ctx* c, int which, const ndt_gicp_params& p, bool raw) {
@@ -60,7 +42,7 @@ static ndt_status gicp_covariances(ndt_ctx* c, int which, const ndt_gicp_params&
     TRY(ensure(c, cv.buf, (size_t)9 * n));
     if (raw) TRY(ensure(c, g.raw, (size_t)9 * n));
     if (which == 0) {
-        TRY(gicp_target_index(c));
+        TRY(target_nn_index(c, "GICP"));
         launch_cov(c, c->target_ptr, n, p, c->fit_ix, cv.buf.p, raw ? g.raw.p : nullptr);
     } else {
         TRY(ensure(c, g.src_ix.hdr, 1));
@@ -68,13 +50,8 @@ static ndt_status gicp_covariances(ndt_ctx* c, int which, const ndt_gicp_params&
         launch_cov(c, c->source.p, n, p, g.src_ix, cv.buf.p, raw ? g.raw.p : nullptr);
     }
     HIPCHK(c, hipGetLastError());
-    int ix_err = 0;  // the index sort's error bits
-    HIPCHK(c, hipMemcpyAsync(&ix_err, &(which == 0 ? c->fit_ix : g.src_ix).hdr.p->pad[0], sizeof(int), hipMemcpyDeviceToHost, c->stream.get()));
-    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
-    if (ix_err) {
-        if (which == 0) c->fit_valid = false;
-        return fail(c, NDT_EDEVICE, "GICP: nearest-neighbour index sort: radix look-back timed out");
-    }
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));  // check_index_sort reads behind a synchronised stream
+    TRY(check_index_sort(c, which == 0 ? c->fit_ix : g.src_ix, "GICP"));
     cv.valid = true;
     cv.gen = gen;
     cv.k = p.k_correspondences;
@@ -84,17 +61,7 @@ static ndt_status gicp_covariances(ndt_ctx* c, int which, const ndt_gicp_params&
 
 static ndt_status gicp_buffers(ndt_ctx* c) {
     GicpRun& g = c->gicp;
-    if (!g.h_state) {  // the device state, its history and the pinned copies: all three or none
-        DevBuf<GicpState> d_state;
-        DevBuf<GicpRecordDev> d_hist;
-        Pinned<GicpState[]> h_state;
-        if (ensure(c, d_state, 1) != NDT_OK || ensure(c, d_hist, kGicpMaxHistory) != NDT_OK ||
-            make_pinned(c, h_state, 2, hipHostMallocDefault) != NDT_OK)
-            return fail(c, NDT_ENOMEM, "GICP state allocation failed");
-        g.d_state = std::move(d_state);
-        g.d_hist = std::move(d_hist);
-        g.h_state = std::move(h_state);
-    }
+    TRY(make_run_state(c, g.d_state, g.d_hist, kGicpMaxHistory, g.h_state, hipHostMallocDefault, "GICP state allocation failed"));
     const int N = c->N;
     TRY(ensure(c, g.match, N)); TRY(ensure(c, g.d2, N)); TRY(ensure(c, g.qt, N)); TRY(ensure(c, g.gp, N));
     TRY(ensure(c, g.M, (size_t)9 * N));
@@ -135,18 +102,7 @@ static ndt_status gicp_graph(ndt_ctx* c, int blocks, int nbp, hipGraphExec_t* ou
     const long long key[16] = {blocks, nbp, c->N, a(c->source.p), a(c->fit_ix.hdr.p), a(c->fit_ix.blk.p), a(c->fit_ix.off.p),
                                a(c->fit_ix.pts.p), a(c->fit_ix.idx.p), a(g.cov_src.buf.p), a(g.cov_tgt.buf.p), a(g.match.p),
                                a(g.d2.p), a(g.qt.p), a(g.gp.p), a(g.M.p)};
-    if (g.graph && std::memcmp(key, g.graph_key, sizeof(key)) == 0) {
-        *out = g.graph.get();
-        return NDT_OK;
-    }
-    if (g.graph) {
-        HIPCHK(c, hipStreamSynchronize(c->stream.get()));
-        g.graph.reset();
-    }
-    TRY(capture_graph(c, "GICP graph capture: ", [&]() -> ndt_status { return gicp_round_body(c, blocks, nbp); }, &g.graph));
-    std::memcpy(g.graph_key, key, sizeof(key));
-    *out = g.graph.get();
-    return NDT_OK;
+    return keyed_graph(c, g.graph, key, "GICP graph capture: ", [&]() -> ndt_status { return gicp_round_body(c, blocks, nbp); }, out);
 }
 
 extern "C" {
@@ -178,7 +134,7 @@ ndt_status ndt_gicp_align(ndt_ctx* c, const ndt_gicp_params* prm, const float gu
     g.n = 0;
     TRY(gicp_covariances(c, 0, p, false));
     TRY(gicp_covariances(c, 1, p, false));
-    TRY(gicp_target_index(c));  // a target unchanged since its covariances: the index may have been dropped since
+    TRY(target_nn_index(c, "GICP"));  // a target unchanged since its covariances: the index may have been dropped since
     TRY(gicp_buffers(c));
     const int N = c->N;
     GicpState* s0 = &g.h_state[1];
@@ -225,12 +181,7 @@ ndt_status ndt_gicp_align(ndt_ctx* c, const ndt_gicp_params* prm, const float gu
         g.rounds += 1;
     }
     if (!finished) return fail(c, NDT_EDEVICE, "GICP did not finish within its round budget");
-    int ix_err = 0;
-    HIPCHK(c, hipMemcpy(&ix_err, &c->fit_ix.hdr.p->pad[0], sizeof(int), hipMemcpyDeviceToHost));
-    if (ix_err) {
-        c->fit_valid = false;
-        return fail(c, NDT_EDEVICE, "GICP: nearest-neighbour index sort: radix look-back timed out");
-    }
+    TRY(check_index_sort(c, c->fit_ix, "GICP"));  // behind the last round's synchronise, which it relies on
     const GicpState& s = g.h_state[0];
     g.hist.resize(std::min(s.hist_count, kGicpMaxHistory));
     if (!g.hist.empty())

@@ -15,15 +15,7 @@ static ndt_status icp_graph(ndt_ctx* c, int run, int nb, hipGraphExec_t* out) {
                                (long long)(uintptr_t)c->fit_ix.idx.p, (long long)(uintptr_t)c->icp.match.p,
                                (long long)(uintptr_t)c->icp.d2.p, (long long)(uintptr_t)c->icp.part.p,
                                (long long)(uintptr_t)c->icp.ticket.p};
-    if (c->icp.graph && std::memcmp(key, c->icp.graph_key, sizeof(key)) == 0) {
-        *out = c->icp.graph.get();
-        return NDT_OK;
-    }
-    if (c->icp.graph) {
-        HIPCHK(c, hipStreamSynchronize(c->stream.get()));
-        c->icp.graph.reset();
-    }
-    TRY(capture_graph(c, "ICP graph capture: ", [&]() -> ndt_status {
+    return keyed_graph(c, c->icp.graph, key, "ICP graph capture: ", [&]() -> ndt_status {
         for (int k = 0; k < run; ++k)
             hipLaunchKernelGGL(k_icp_pass, dim3(nb), dim3(kIcpBlock), 0, c->stream.get(), c->icp.x.p, c->N, c->icp.d_state.p, c->fit_ix.hdr.p, c->fit_ix.blk.p,
                                c->fit_ix.off.p, c->fit_ix.pts.p, c->fit_ix.idx.p, c->icp.match.p, c->icp.d2.p, c->icp.part.p,
@@ -31,10 +23,7 @@ static ndt_status icp_graph(ndt_ctx* c, int run, int nb, hipGraphExec_t* out) {
         const hipError_t e = hipMemcpyAsync(&c->icp.h_state[0], c->icp.d_state.p, sizeof(IcpState), hipMemcpyDeviceToHost, c->stream.get());
         if (e != hipSuccess) return fail(c, NDT_EDEVICE, std::string("ICP graph capture: ") + hipGetErrorString(e));
         return NDT_OK;
-    }, &c->icp.graph));
-    std::memcpy(c->icp.graph_key, key, sizeof(key));
-    *out = c->icp.graph.get();
-    return NDT_OK;
+    }, out);
 }
 
 extern "C" {
@@ -62,33 +51,9 @@ ndt_status ndt_icp_align(ndt_ctx* c, const ndt_icp_params* prm, const float gues
     if (c->al_inflight) return fail(c, NDT_EINVAL, "an asynchronous align is in flight (ndt_align_wait first)");
     TRY(set_dev(c));
     TRY(flush_source(c));
-    // the target's nearest-neighbour index (getFitnessScore's), with the points' original indices from now on
-    if (!c->icp.used) {
-        c->icp.used = true;
-        c->fit_valid = false;  // rebuilt behind the fit lane's queued queries (FIFO)
-    }
-    TRY(ensure_fit_index(c));
-    {
-        std::string msg;
-        const ndt_status st = c->lanes.fit_worker->take_error(&msg);  // the index build has been issued
-        if (st != NDT_OK) {
-            c->fit_valid = false;
-            c->lanes.fit_pending = false;
-            return fail(c, st, "ICP: nearest-neighbour index: " + msg);
-        }
-    }
-    HIPCHK(c, hipStreamWaitEvent(c->stream.get(), c->lanes.ev_fit_tgt.get(), 0));
-    if (!c->icp.h_state) {  // the device state, its history and the pinned copies: all three or none
-        DevBuf<IcpState> d_state;
-        DevBuf<IcpRecordDev> d_hist;
-        Pinned<IcpState[]> h_state;
-        if (ensure(c, d_state, 1) != NDT_OK || ensure(c, d_hist, kIcpMaxHistory) != NDT_OK ||
-            make_pinned(c, h_state, 2, hipHostMallocCoherent) != NDT_OK)
-            return fail(c, NDT_ENOMEM, "ICP state allocation failed");
-        c->icp.d_state = std::move(d_state);
-        c->icp.d_hist = std::move(d_hist);
-        c->icp.h_state = std::move(h_state);
-    }
+    TRY(target_nn_index(c, "ICP"));  // getFitnessScore's index, with the points' original indices from now on
+    TRY(make_run_state(c, c->icp.d_state, c->icp.d_hist, kIcpMaxHistory, c->icp.h_state, hipHostMallocCoherent,
+                       "ICP state allocation failed"));
     const int N = c->N;
     const int nb = std::max(1, std::min(ceil_div(N, kIcpTeams), kIcpMaxBlocks));
     TRY(ensure(c, c->icp.x, N)); TRY(ensure(c, c->icp.match, N)); TRY(ensure(c, c->icp.d2, N));
@@ -145,12 +110,7 @@ ndt_status ndt_icp_align(ndt_ctx* c, const ndt_icp_params* prm, const float gues
         c->ms_align = ms;
     }
     if (!finished) return fail(c, NDT_EDEVICE, "ICP did not finish within its iteration budget");
-    int ix_err = 0;  // the index sort's error bits, as k_fitness reports them through its count
-    HIPCHK(c, hipMemcpy(&ix_err, &c->fit_ix.hdr.p->pad[0], sizeof(int), hipMemcpyDeviceToHost));
-    if (ix_err) {
-        c->fit_valid = false;
-        return fail(c, NDT_EDEVICE, "ICP: nearest-neighbour index sort: radix look-back timed out");
-    }
+    TRY(check_index_sort(c, c->fit_ix, "ICP"));  // behind the last round's synchronise, which it relies on
     const IcpState& s = c->icp.h_state[0];
     c->icp.hist.resize(std::min(s.hist_count, kIcpMaxHistory));
     if (!c->icp.hist.empty())

@@ -143,6 +143,38 @@ ndt_status ensure_fit_index(ndt_ctx* c) {
     return NDT_OK;
 }
 
+// The target's index with the points' original indices (ICP, GICP), built and visible to the main stream; prefix names
+// the caller in the error text.
+ndt_status target_nn_index(ndt_ctx* c, const char* prefix) {
+    if (!c->icp.used) {  // the index carries the original-index word from now on
+        c->icp.used = true;
+        c->fit_valid = false;  // rebuilt behind the fit lane's queued queries (FIFO)
+    }
+    TRY(ensure_fit_index(c));
+    std::string msg;
+    const ndt_status st = c->lanes.fit_worker->take_error(&msg);  // the index build has been issued
+    if (st != NDT_OK) {
+        c->fit_valid = false;
+        c->lanes.fit_pending = false;
+        return fail(c, st, std::string(prefix) + ": nearest-neighbour index: " + msg);
+    }
+    HIPCHK(c, hipStreamWaitEvent(c->stream.get(), c->lanes.ev_fit_tgt.get(), 0));
+    return NDT_OK;
+}
+
+// The error bits of ix's sort (GridHeader::pad[0], as k_fitness reports them through its count); a flagged target index
+// is dropped.  The caller has synchronised the main stream behind the kernels that read ix, so the read is one blocking
+// copy (an asynchronous copy into pageable memory and a second synchronise cost an align some 10 us more).
+ndt_status check_index_sort(ndt_ctx* c, const NNIndex& ix, const char* prefix) {
+    int ix_err = 0;
+    HIPCHK(c, hipMemcpy(&ix_err, &ix.hdr.p->pad[0], sizeof(int), hipMemcpyDeviceToHost));
+    if (ix_err) {
+        if (&ix == &c->fit_ix) c->fit_valid = false;
+        return fail(c, NDT_EDEVICE, std::string(prefix) + ": nearest-neighbour index sort: radix look-back timed out");
+    }
+    return NDT_OK;
+}
+
 // getFitnessScore of N device points src (the ctx's source, or a caller cloud that stays valid until the result call)
 static ndt_status fitness_enqueue(ndt_ctx* c, const float* T, double max_range, const float4* src, int N, bool ctx_source,
                                   bool index_ready = false) {

@@ -3,14 +3,14 @@
 // One k_icp_pass launch is one ICP iteration:
 //   * every workgroup first applies the previous iteration's transform to its points (pcl::transformPointCloud in f32,
 //     in place and cumulative, as PCL's loop does) — the apply step fused into the next pass;
-//   * CorrespondenceEstimation: the exact nearest target point of each query over ALL target points, by the walk of
-//     k_fitness (voxel_build.hip: 16-lane team per query, 3x3x3 cube, 5x5x5 cube, block shells) over the same index,
-//     tracking the argmin beside the minimum; equal f32 distances go to the lowest target index in the caller's order
-//     (the index build carries that index as a fifth word beside the sorted points);
+//   * CorrespondenceEstimation: the exact nearest target point of each query over ALL target points, by the walk
+//     k_fitness uses (ndt_nnwalk.h: 16-lane team per query, 3x3x3 cube, 5x5x5 cube, block shells) over the same index,
+//     with the argmin tracker; equal f32 distances go to the lowest target index in the caller's order (the index
+//     build carries that index as a fifth word beside the sorted points);
 //   * 17 f64 sums over the kept pairs (n, sum d2, sum p, sum q, sum p q^T), one per lane of the team, reduced per wave,
-//     then through LDS, stored as write-through partials; the last workgroup (ticket) sums the partials in index order
-//     and runs the rest of the iteration: pair-count test, Umeyama estimate (TransformationEstimationSVD), the final
-//     transform, DefaultConvergenceCriteria, the history record.
+//     then through LDS, stored as write-through partials; the last workgroup (ticket, ndt_lastwg.h) sums the partials in
+//     index order and runs the rest of the iteration: pair-count test, Umeyama estimate (TransformationEstimationSVD),
+//     the final transform, DefaultConvergenceCriteria, the history record.
 // A launch that finds the state done returns at once, so fixed-length runs of launches can be one graph.
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -19,11 +19,14 @@
 #include "ndt_linalg.h"
 #include "ndt_icp.h"
 #include "ndt_nnwalk.h"
+#include "ndt_lastwg.h"
 #include "ndt_kernels.h"
 
 namespace ndt {
 
 namespace {
+
+static_assert(kIcpTeam == kNnTeam, "k_icp_pass's teams are nn_walk's");
 
 __device__ __forceinline__ double det3(const double* m) {
     return m[0] * (m[4] * m[8] - m[7] * m[5]) - m[3] * (m[1] * m[8] - m[7] * m[2]) + m[6] * (m[1] * m[5] - m[4] * m[2]);
@@ -135,10 +138,8 @@ __global__ __launch_bounds__(kIcpBlock) NDT_ICP_OCC void k_icp_pass(float4* __re
             if (t == 0) X[i] = p;
         }
         const float q[3] = {p.x, p.y, p.z};
-        Arg a = {INFINITY, -1, INT_MAX};
-        if (!empty) {
-            nn_walk(q, t, h, db, nbk, cell, block_table, cell_off, fit_pts, fit_idx, a);
-        }
+        NnArg a = {INFINITY, -1, INT_MAX, fit_idx};
+        if (!empty) nn_walk(q, t, h, db, nbk, cell, block_table, cell_off, fit_pts, a);
         const bool keep = a.pos >= 0 && (double)a.d <= max_corr2;
         if (t == 0) {
             match[i] = keep ? a.orig : -1;
@@ -155,8 +156,6 @@ __global__ __launch_bounds__(kIcpBlock) NDT_ICP_OCC void k_icp_pass(float4* __re
     // ---- per wave: the four teams' sums (lanes t, t + 16, t + 32, t + 48), then the waves through LDS in wave order
     constexpr int kWaves = kIcpBlock / 64;
     __shared__ double s_part[kWaves][kIcpSums];
-    __shared__ double s_tot[kIcpSums];
-    __shared__ int s_last;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     acc += __shfl_xor(acc, 16);
     acc += __shfl_xor(acc, 32);
@@ -164,45 +163,9 @@ __global__ __launch_bounds__(kIcpBlock) NDT_ICP_OCC void k_icp_pass(float4* __re
     cnt += __shfl_xor(cnt, 32);
     if (lane < kIcpTeam) s_part[wave][lane] = acc;
     if (lane == 0) s_part[wave][16] = (double)cnt;
-    __syncthreads();
-    const int nb = gridDim.x;
-    // partials stored write-through and drained before the ticket, the ticket taker acquires (the hand-off of k_fitness);
-    // the storing threads are all lanes of wave 0, whose drain covers them
-    if (threadIdx.x < 64) {
-        if (threadIdx.x < kIcpSums) {
-            double v = s_part[0][threadIdx.x];
-            for (int w = 1; w < kWaves; ++w) v += s_part[w][threadIdx.x];
-            __hip_atomic_store(partials + (size_t)threadIdx.x * nb + blockIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (threadIdx.x == 0)
-            s_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)nb - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // ---- last workgroup: the partials in index order (thread-strided groups of kIcpBlock, then a fixed tree)
-    __syncthreads();  // s_part is reused
-    for (int k = 0; k < kIcpSums; ++k) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < nb; b += kIcpBlock) v += partials[(size_t)k * nb + b];
-        for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-        if (lane == 0) s_part[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kIcpSums) {
-        double v = s_part[0][threadIdx.x];
-        for (int w = 1; w < kWaves; ++w) v += s_part[w][threadIdx.x];
-        s_tot[threadIdx.x] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        *ticket = 0u;  // re-armed for the next launch
-        double S[kIcpSums];
-        for (int k = 0; k < kIcpSums; ++k) S[k] = s_tot[k];
-        icp_control(S, st, hist);
-    }
+    // ---- the workgroups' partials, summed in index order by the last workgroup, whose thread 0 runs the rest
+    double S[kIcpSums];
+    if (last_workgroup_sums<kIcpSums, kIcpBlock>(s_part, partials, ticket, S)) icp_control(S, st, hist);
 }
 
 }  // namespace ndt

@@ -242,8 +242,8 @@ void ndt_destroy(ndt_ctx* c) {
     c->lanes.ins_worker.reset();
     for (hipStream_t st : {c->stream.get(), c->lanes.fit_stream.get(), c->lanes.ins_stream.get()}) if (st) (void)hipStreamSynchronize(st);
     invalidate_graph(c);
-    c->icp.graph.reset();
-    c->gicp.graph.reset();
+    c->icp.graph.exec.reset();
+    c->gicp.graph.exec.reset();
     delete c;
 }
 

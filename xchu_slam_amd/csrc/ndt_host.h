@@ -53,6 +53,13 @@ using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
 using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
 using GraphExec = std::unique_ptr<std::remove_pointer_t<hipGraphExec_t>, GraphExecDestroy>;
 
+// A captured graph kept with the key it was captured for: the launch shape and every buffer its nodes name that can be
+// reallocated between two uses (keyed_graph)
+template <int N> struct KeyedGraph {
+    GraphExec exec;
+    long long key[N] = {0};
+};
+
 struct Scratch {
     DevBuf<int> k0, v0, k1, v1, radix_aux, seg_start, flags, cloud_idx;
     DevBuf<int2> cloud_span;
@@ -232,8 +239,7 @@ struct IcpRun {
     float final_tf[16] = {0};
     int n = 0;                          // source points of the last ICP align
     std::vector<IcpRecordDev> hist;
-    GraphExec graph;
-    long long graph_key[12] = {0};
+    KeyedGraph<12> graph;               // one run of passes and the state read-back
 };
 
 // host_gicp.hip — Generalized-ICP (ndt_gicp_align): the source's own neighbour index, the per-point covariances of both
@@ -261,8 +267,7 @@ struct GicpRun {
     Pinned<GicpState[]> h_state;
     int n = 0;                          // source points of the last GICP align
     unsigned long long src_gen = 0;     // the source that align ran over (the hooks refuse another)
-    GraphExec graph;                    // one round of launches and the state read-back
-    long long graph_key[16] = {0};
+    KeyedGraph<16> graph;               // one round of launches and the state read-back
     int launches = 0, rounds = 0;       // of the last align
     std::vector<GicpRecordDev> hist;
 };
@@ -270,7 +275,7 @@ struct GicpRun {
 // Member order is part of the design: members are released in reverse order of declaration (delete c, the last step of
 // ndt_destroy, after it has joined the lane workers, synchronised the three streams and dropped the graph execs).  So
 // the main stream is declared before everything that is queued or released on it, capture_mu before the lane workers
-// that hold its address, and the graph execs (icp.graph, graphs) after the buffers their nodes name.
+// that hold its address, and the graph execs (icp.graph, gicp.graph, graphs) after the buffers their nodes name.
 struct ndt_ctx {
     ndt_params prm{};
     int device = 0;
@@ -466,6 +471,23 @@ inline ndt_status make_stream(ndt_ctx* c, Stream& out, int priority) {
     return NDT_OK;
 }
 
+// The device state of a run, its device history and the pinned pair of state copies, made together or not at all
+// (what: the error text when one of them cannot be allocated)
+template <typename S, typename R>
+ndt_status make_run_state(ndt_ctx* c, DevBuf<S>& d_state, DevBuf<R>& d_hist, size_t hist_cap, Pinned<S[]>& h_state,
+                          unsigned pinned_flags, const char* what) {
+    if (h_state) return NDT_OK;
+    DevBuf<S> ds;
+    DevBuf<R> dh;
+    Pinned<S[]> hs;
+    if (ensure(c, ds, 1) != NDT_OK || ensure(c, dh, hist_cap) != NDT_OK || make_pinned(c, hs, 2, pinned_flags) != NDT_OK)
+        return fail(c, NDT_ENOMEM, what);
+    d_state = std::move(ds);
+    d_hist = std::move(dh);
+    h_state = std::move(hs);
+    return NDT_OK;
+}
+
 // the caller-set options handed to a helper context of the batched replay; tile_tickets stays set once a look-back of
 // the helper's own timed out
 inline void hand_options(ndt_ctx* h, const ndt_ctx* c) {
@@ -508,10 +530,27 @@ void invalidate_graph(ndt_ctx* c);
 ndt_status copy16(ndt_ctx* c, hipStream_t stream, void* dst, const void* src, size_t bytes);
 ndt_status flush_source(ndt_ctx* c);
 ndt_status capture_graph(ndt_ctx* c, const char* end_what, const std::function<ndt_status()>& body, GraphExec* out);
+// g's graph when it was captured for this key; else the main stream synchronised, the old graph dropped and body captured
+template <int N>
+ndt_status keyed_graph(ndt_ctx* c, KeyedGraph<N>& g, const long long (&key)[N], const char* end_what,
+                       const std::function<ndt_status()>& body, hipGraphExec_t* out) {
+    if (!g.exec || std::memcmp(key, g.key, sizeof(key)) != 0) {
+        if (g.exec) {
+            HIPCHK(c, hipStreamSynchronize(c->stream.get()));
+            g.exec.reset();
+        }
+        TRY(capture_graph(c, end_what, body, &g.exec));
+        std::memcpy(g.key, key, sizeof(key));
+    }
+    *out = g.exec.get();
+    return NDT_OK;
+}
 // host_lanes.hip
 ndt_status main_after_fit(ndt_ctx* c, bool source);
 ndt_status enqueue_nn_index(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, float cell, NNIndex& ix, bool want_idx = false);
 ndt_status ensure_fit_index(ndt_ctx* c);
+ndt_status target_nn_index(ndt_ctx* c, const char* prefix);
+ndt_status check_index_sort(ndt_ctx* c, const NNIndex& ix, const char* prefix);
 // host_front_end.hip
 ndt_status voxel_downsample_dev(ndt_ctx* c, const float4* in, size_t n, float leaf, float4* out, size_t* n_out);
 // host_sc.hip

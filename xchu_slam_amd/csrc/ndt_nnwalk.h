@@ -1,28 +1,34 @@
-// ndt_nnwalk.h — the exact nearest-neighbour walk of one 16-lane team over an NNIndex, with the argmin and the
-// lowest-original-index tie rule (device only).  Shared by k_icp_pass (icp.hip) and k_gicp_pairs (gicp.hip).
+// ndt_nnwalk.h — the exact nearest-neighbour walk of one 16-lane team over an NNIndex (device only): the 3x3x3 cube
+// around the query cell, the 5x5x5 cube, then shells of 8x8x8-cell blocks.  The one copy of that walk, shared by
+// k_fitness (fitness.hip), k_icp_pass (icp.hip) and k_gicp_pairs (gicp.hip).
 //
-// The walk is k_fitness's (voxel_build.hip: 3x3x3 cube, 5x5x5 cube, block shells) tracking the argmin beside the
-// minimum; equal f32 distances go to the lowest index in the caller's order (the index build carries that index as a
-// fifth word beside the sorted points).
+// What a caller keeps of the candidates is its tracker's business.  A tracker supplies take(d, j, ix) (candidate j of
+// the index at squared distance d), team(ix) (the 16-lane reduce that leaves it team-uniform), the current distance d,
+// the two comparisons the walk stops and prunes by, settled(bound2) and skip(lb), and index(): the index's fifth word
+// if it reads one.  The walk takes that pointer from the tracker once and hands it back as ix: read through the
+// tracker's reference at every candidate instead, the compiler allocates k_icp_pass's registers differently (same
+// count) and the pass comes out 0.8 % slower; this way its code is the walk's code of before the trackers.
+//   NnMin  (getFitnessScore) keeps the minimum alone.  A point that could only tie changes nothing, so the walk may
+//          stop at best <= bound^2 and pass over a block whose lower bound equals the best.
+//   NnArg  (ICP, GICP) keeps the argmin; equal f32 distances go to the lowest index in the caller's order (the index
+//          build carries that index as a fifth word beside the sorted points).  A point that could only tie may still
+//          win on its index and must be seen: the walk stops only at best < bound^2 and passes over a block only when
+//          its lower bound is above the best.
+// Distances are FLANN's L2_Simple in f32, (dx^2 + dy^2) + dz^2; the minimum depends neither on the visiting order nor on
+// the lane split, and with the tie rule neither does the argmin.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include "ndt_types.h"
-#include "ndt_icp.h"
 
 namespace ndt {
 
-constexpr int kIcpU = 8;      // point loads in flight per lane
-constexpr int kIcpCells = 2;  // ring-cube cells per lane per step
+constexpr int kNnTeam = NDT_FIT_TEAM;  // lanes per query (ndt_types.h)
+constexpr int kNnU = 8;                // point loads in flight per lane (clamped repeats past a range's end)
+constexpr int kNnCells = 2;            // ring-cube cells per lane per step: their table, offset and point loads issued together
 
-// running argmin of one lane: squared distance, position in the index, original target index (-2: not loaded yet)
-struct Arg {
-    float d;
-    int pos, orig;
-};
-
-// FLANN L2_Simple in f32, as l2_simple of voxel_build.hip
-__device__ __forceinline__ float icp_l2(const float4 t, const float q[3]) {
+// FLANN L2_Simple in f32
+__device__ __forceinline__ float nn_l2(const float4 t, const float q[3]) {
     float d = 0.f, u;
     u = t.x - q[0]; d += u * u;
     u = t.y - q[1]; d += u * u;
@@ -30,45 +36,75 @@ __device__ __forceinline__ float icp_l2(const float4 t, const float q[3]) {
     return d;
 }
 
-// candidate j at distance d; a tie goes to the lower original index (loaded only then); a repeated j changes nothing
-__device__ __forceinline__ void arg_take(Arg& a, float d, int j, const int* __restrict__ idx) {
-    if (d < a.d) {
-        a.d = d;
-        a.pos = j;
-        a.orig = -2;
-    } else if (d == a.d && j != a.pos) {
-        if (a.orig == -2) a.orig = idx[a.pos];
-        const int oj = idx[j];
-        if (oj < a.orig) {
-            a.pos = j;
-            a.orig = oj;
+// running minimum of one lane
+struct NnMin {
+    float d;
+    __device__ __forceinline__ const int* index() const { return nullptr; }  // reads no fifth word
+    // a repeated candidate is harmless for a minimum
+    __device__ __forceinline__ void take(float v, int, const int*) { d = fminf(d, v); }
+    __device__ __forceinline__ void team(const int*) {
+        for (int m = kNnTeam / 2; m > 0; m >>= 1) d = fminf(d, __shfl_xor(d, m, kNnTeam));
+    }
+    // every unvisited point is at least sqrt(bound2) away: none can be closer, and one as close leaves the minimum as it is
+    __device__ __forceinline__ bool settled(float bound2) const { return d <= bound2; }
+    // a block no closer than the minimum cannot lower it
+    __device__ __forceinline__ bool skip(float lb) const { return lb >= d; }
+};
+
+// running argmin of one lane: squared distance, position in the index, original target index (-2: not loaded yet),
+// and the index's fifth word (per sorted point: its index in the caller's order).  Starts as {INFINITY, -1, INT_MAX, idx};
+// pos stays -1 when no point was found.
+struct NnArg {
+    float d;
+    int pos, orig;
+    const int* __restrict__ idx;
+    __device__ __forceinline__ const int* index() const { return idx; }
+    // candidate j at distance v; a tie goes to the lower original index (loaded only then); a repeated j changes nothing
+    __device__ __forceinline__ void take(float v, int j, const int* __restrict__ ix) {
+        if (v < d) {
+            d = v;
+            pos = j;
+            orig = -2;
+        } else if (v == d && j != pos) {
+            if (orig == -2) orig = ix[pos];
+            const int oj = ix[j];
+            if (oj < orig) {
+                pos = j;
+                orig = oj;
+            }
         }
     }
-}
-
-// the team's argmin in every lane ((d, orig) is a strict order over distinct points: every lane ends with the same one)
-__device__ __forceinline__ void arg_team(Arg& a, const int* __restrict__ idx) {
-    if (a.orig == -2) a.orig = idx[a.pos];
-    for (int m = kIcpTeam / 2; m > 0; m >>= 1) {
-        const float od = __shfl_xor(a.d, m, kIcpTeam);
-        const int oo = __shfl_xor(a.orig, m, kIcpTeam);
-        const int op = __shfl_xor(a.pos, m, kIcpTeam);
-        if (od < a.d || (od == a.d && oo < a.orig)) {
-            a.d = od;
-            a.orig = oo;
-            a.pos = op;
+    // the team's argmin in every lane ((d, orig) is a strict order over distinct points: every lane ends with the same one)
+    __device__ __forceinline__ void team(const int* __restrict__ ix) {
+        if (orig == -2) orig = ix[pos];
+        for (int m = kNnTeam / 2; m > 0; m >>= 1) {
+            const float od = __shfl_xor(d, m, kNnTeam);
+            const int oo = __shfl_xor(orig, m, kNnTeam);
+            const int op = __shfl_xor(pos, m, kNnTeam);
+            if (od < d || (od == d && oo < orig)) {
+                d = od;
+                orig = oo;
+                pos = op;
+            }
         }
     }
-}
+    // strictly closer than every unvisited point: none of them can tie with the match (at d == bound2 one could, and
+    // could carry the lower index)
+    __device__ __forceinline__ bool settled(float bound2) const { return d < bound2; }
+    // a block that could only tie is still scanned: its point may carry the lower index
+    __device__ __forceinline__ bool skip(float lb) const { return lb > d; }
+};
 
-// up to kIcpCells cells of a ring cube (cell k0, k0 + kIcpTeam, ...: one lane's share), as cells_min of voxel_build.hip
-__device__ __forceinline__ void cells_arg(int k0, int ncell, int side, int ring, const int c[3], const int db[3], const int nbk[3],
-                                          const int* __restrict__ block_table, const int* __restrict__ cell_off,
-                                          const float4* __restrict__ pts, const int* __restrict__ idx, const float q[3], Arg& a) {
-    int occ[kIcpCells], lc[kIcpCells], b[kIcpCells], n[kIcpCells];
+// up to kNnCells cells of a ring cube (cell k0, k0 + kNnTeam, ...: one lane's share), each level of loads (block table,
+// cell offsets, points) issued for all of them before any is consumed
+template <class Tracker>
+__device__ __forceinline__ void nn_cells(int k0, int ncell, int side, int ring, const int c[3], const int db[3], const int nbk[3],
+                                         const int* __restrict__ block_table, const int* __restrict__ cell_off,
+                                         const float4* __restrict__ pts, const int* __restrict__ idx, const float q[3], Tracker& a) {
+    int occ[kNnCells], lc[kNnCells], b[kNnCells], n[kNnCells];
 #pragma unroll
-    for (int i = 0; i < kIcpCells; ++i) {
-        const int k = k0 + i * kIcpTeam;
+    for (int i = 0; i < kNnCells; ++i) {
+        const int k = k0 + i * kNnTeam;
         const int x = c[0] + k % side - ring, y = c[1] + (k / side) % side - ring, z = c[2] + k / (side * side) - ring;
         const bool in = k < ncell && x >= 0 && y >= 0 && z >= 0 && x < db[0] && y < db[1] && z < db[2];
         lc[i] = ((z & 7) << 6) | ((y & 7) << 3) | (x & 7);
@@ -76,7 +112,7 @@ __device__ __forceinline__ void cells_arg(int k0, int ncell, int side, int ring,
     }
     int tot = 0;
 #pragma unroll
-    for (int i = 0; i < kIcpCells; ++i) {
+    for (int i = 0; i < kNnCells; ++i) {
         b[i] = 0;
         n[i] = 0;
         if (occ[i] >= 0) {
@@ -86,15 +122,16 @@ __device__ __forceinline__ void cells_arg(int k0, int ncell, int side, int ring,
         }
         tot += n[i];
     }
-    for (int j = 0; j < tot; j += kIcpU) {
-        float4 p[kIcpU];
-        int at[kIcpU];
+    // the cells' point ranges walked as one sequence, kNnU loads in flight (the last point repeated past the end)
+    for (int j = 0; j < tot; j += kNnU) {
+        float4 p[kNnU];
+        int at[kNnU];
 #pragma unroll
-        for (int u = 0; u < kIcpU; ++u) {
+        for (int u = 0; u < kNnU; ++u) {
             int v = min(j + u, tot - 1);
             int id = 0;
 #pragma unroll
-            for (int i = 0; i < kIcpCells; ++i) {
+            for (int i = 0; i < kNnCells; ++i) {
                 if (v >= 0 && v < n[i]) id = b[i] + v;
                 v -= n[i];
             }
@@ -102,14 +139,23 @@ __device__ __forceinline__ void cells_arg(int k0, int ncell, int side, int ring,
             p[u] = pts[id];
         }
 #pragma unroll
-        for (int u = 0; u < kIcpU; ++u) arg_take(a, icp_l2(p[u], q), at[u], idx);
+        for (int u = 0; u < kNnU; ++u) a.take(nn_l2(p[u], q), at[u], idx);
     }
 }
 
-// The nearest point of a non-empty index to q, for lane t of a team: a ends team-uniform (pos -1: none found).
+// The nearest point of a non-empty index to q, for lane t of a team: a ends team-uniform.
+//   phase 1: the cubes of radius 1 and 2 around the query cell, one cell per lane per step (the inner cells of the second
+//     scanned again: both trackers are idempotent).  After the cube of radius r every unvisited point lies in a cell at
+//     Chebyshev distance >= r + 1: at least the query's distance to the nearest cube face away (a small slack covers
+//     binning round-off), so the team stops once its tracker is settled below that;
+//   phase 2 (no point that close): square shells of 8x8x8-cell blocks; each occupied block the tracker cannot skip is
+//     scanned as one contiguous range split over the lanes; after block shell r every unvisited point is at least 8r
+//     cells away along some axis.
+template <class Tracker>
 __device__ __forceinline__ void nn_walk(const float q[3], int t, const GridHeader* __restrict__ h, const int db[3], const int nbk[3],
                                         float cell, const int* __restrict__ block_table, const int* __restrict__ cell_off,
-                                        const float4* __restrict__ fit_pts, const int* __restrict__ fit_idx, Arg& a) {
+                                        const float4* __restrict__ fit_pts, Tracker& a) {
+    const int* __restrict__ idx = a.index();
     int c[3];
     for (int k = 0; k < 3; ++k) c[k] = (int)(floorf(q[k] * h->inv_leaf[k]) - (float)h->min_b[k]);
     const float slack = 1e-4f * cell + 4e-7f * (fabsf(q[0]) + fabsf(q[1]) + fabsf(q[2]));
@@ -120,27 +166,26 @@ __device__ __forceinline__ void nn_walk(const float q[3], int t, const GridHeade
         rmax = max(rmax, max(c[k], db[k] - 1 - c[k]));
     }
     rmax = max(rmax, r0);
+    // distance from the query to the nearest face of its own cell
     float face = cell;
     for (int k = 0; k < 3; ++k) {
         const float lo = (float)(c[k] + h->min_b[k]) * h->leaf[k];
         face = fminf(face, fminf(fmaxf(q[k] - lo, 0.f), fmaxf(lo + h->leaf[k] - q[k], 0.f)));
     }
     bool done = false;
-    // ---- phase 1: the cubes of radius 1 and 2 around the query cell, one cell per lane per step
+    // ---- phase 1
     if (r0 <= 2) {
         for (int ring = 1; ring <= 2 && !done; ++ring) {
             const int side = 2 * ring + 1;
             const int ncell = side * side * side;
-            for (int k0 = t; k0 < ncell; k0 += kIcpCells * kIcpTeam)
-                cells_arg(k0, ncell, side, ring, c, db, nbk, block_table, cell_off, fit_pts, fit_idx, q, a);
-            arg_team(a, fit_idx);
-            // every unvisited point is at least `bound` away; strictly closer than that and no unvisited point can
-            // tie with the match
+            for (int k0 = t; k0 < ncell; k0 += kNnCells * kNnTeam)
+                nn_cells(k0, ncell, side, ring, c, db, nbk, block_table, cell_off, fit_pts, idx, q, a);
+            a.team(idx);
             const float bound = fmaxf(0.f, face + (float)ring * cell - slack);
-            done = a.d < bound * bound || ring >= rmax;
+            done = a.settled(bound * bound) || ring >= rmax;
         }
     }
-    // ---- phase 2: block shells, each candidate block's points split over the team
+    // ---- phase 2
     if (!done) {
         int cb[3], b0 = 0, bmax = 0;
         for (int k = 0; k < 3; ++k) {
@@ -153,6 +198,7 @@ __device__ __forceinline__ void nn_walk(const float q[3], int t, const GridHeade
         auto visit_block = [&](int x, int y, int z) {
             const int occ = block_table[((z * nbk[1] + y) * nbk[0]) + x];
             if (occ < 0) return;
+            // lower bound: per-axis cell gap between the query cell and the block's cells
             const int bx[3] = {x, y, z};
             float lb = 0.f;
             for (int k = 0; k < 3; ++k) {
@@ -161,17 +207,18 @@ __device__ __forceinline__ void nn_walk(const float q[3], int t, const GridHeade
                 const float g = fmaxf(0.f, (float)gap * cell - slack);
                 lb += g * g;
             }
-            if (lb > a.d) return;  // a is team-uniform here; a block that could only tie is still scanned
+            if (a.skip(lb)) return;  // a is team-uniform here
             const int* off = cell_off + (size_t)occ * (kFitBlockCells + 1);
             const int e = off[kFitBlockCells];
-            for (int j = off[0] + t; j < e; j += kIcpU * kIcpTeam) {
-                float4 pp[kIcpU];
+            // a block holds up to hundreds of points: kNnU loads in flight per lane, not one round trip per point
+            for (int j = off[0] + t; j < e; j += kNnU * kNnTeam) {
+                float4 pp[kNnU];
 #pragma unroll
-                for (int u = 0; u < kIcpU; ++u) pp[u] = fit_pts[min(j + u * kIcpTeam, e - 1)];
+                for (int u = 0; u < kNnU; ++u) pp[u] = fit_pts[min(j + u * kNnTeam, e - 1)];
 #pragma unroll
-                for (int u = 0; u < kIcpU; ++u) arg_take(a, icp_l2(pp[u], q), min(j + u * kIcpTeam, e - 1), fit_idx);
+                for (int u = 0; u < kNnU; ++u) a.take(nn_l2(pp[u], q), min(j + u * kNnTeam, e - 1), idx);
             }
-            arg_team(a, fit_idx);
+            a.team(idx);
         };
         for (int r = b0; r <= bmax; ++r) {
             const int lo2 = max(cb[2] - r, 0), hi2 = min(cb[2] + r, nbk[2] - 1);
@@ -187,7 +234,7 @@ __device__ __forceinline__ void nn_walk(const float q[3], int t, const GridHeade
                     }
                 }
             const float bound = fmaxf(0.f, (float)(8 * r) * cell - slack);
-            if (a.d < bound * bound) break;
+            if (a.settled(bound * bound)) break;
         }
     }
 }

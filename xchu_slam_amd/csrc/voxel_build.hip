@@ -1264,314 +1264,6 @@ __global__ __launch_bounds__(kBlock) void k_fit_tables(const int* __restrict__ f
         for (int j = l + 1; j <= kFitBlockCells; ++j) off[j] = fit_start[s + 1];
 }
 
-// Exact nearest neighbour of each transformed source point (pcl::transformPointCloud in f32) over all target
-// points, one 16-lane team per query.  The index is block-major (8x8x8-cell blocks, cells x-fastest inside a block),
-// so the cells of an x-row inside one block hold one contiguous range of points: a row of up to 5 cells is at most two
-// ranges, found with one block-table load and two offset loads per block.  Search order:
-//   phase 1: the 3x3x3 cube around the query cell as 9 x-rows (one per lane), then the 5x5x5 cube as 25 x-rows (its
-//     inner cells scanned again: the minimum is idempotent); after the cube of radius r every unvisited point lies in
-//     a cell at Chebyshev distance >= r+1, i.e. at least r cells away along some axis (a small slack covers binning
-//     round-off), so the team stops once its best squared distance is below that;
-//   phase 2 (no point that close): square shells of 8x8x8-cell blocks; each occupied block whose lower bound
-//     beats the best is scanned as one contiguous range split over the lanes; after block shell r every unvisited
-//     point is at least 8r cells away along some axis.
-// Distances are FLANN's L2_Simple in float ((dx^2 + dy^2) + dz^2); the minimum does not depend on the visiting
-// order or on the lane split.
-#ifndef NDT_FIT_RANGE_U
-#define NDT_FIT_RANGE_U 8
-#endif
-constexpr int kFitTeam = NDT_FIT_TEAM;  // lanes per query (ndt_types.h)
-constexpr int kFitBlock = NDT_FIT_BLOCK;  // threads per k_fitness workgroup (ndt_types.h)
-constexpr int kFitP2 = 8;  // block-scan loads in flight per lane
-
-__device__ __forceinline__ float team_min(float v) {
-    for (int m = kFitTeam / 2; m > 0; m >>= 1) v = fminf(v, __shfl_xor(v, m, kFitTeam));
-    return v;
-}
-
-__device__ __forceinline__ float l2_simple(const float4 t, const float q[3]) {
-    float d = 0.f, u;
-    u = t.x - q[0]; d += u * u;
-    u = t.y - q[1]; d += u * u;
-    u = t.z - q[2]; d += u * u;
-    return d;
-}
-
-// min over the points [b, e) of the index, four loads in flight (the last point repeated past e: harmless for a
-// minimum) instead of one round trip per point (a localmap cell holds one point per keyframe that saw it)
-__device__ __forceinline__ float range_min(const float4* __restrict__ pts, int b, int e, const float q[3], float best) {
-    constexpr int U = NDT_FIT_RANGE_U;
-    for (int j = b; j < e; j += U) {
-        float4 p[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) p[u] = pts[min(j + u, e - 1)];
-#pragma unroll
-        for (int u = 0; u < U; ++u) best = fminf(best, l2_simple(p[u], q));
-    }
-    return best;
-}
-
-// min over the points of the cells (xa..xb, y, z), 0 <= xa <= xb < xa + 8 inside the grid: at most two blocks
-__device__ __forceinline__ float row_min(int xa, int xb, int y, int z, const int nbk[3], const int* __restrict__ block_table,
-                                         const int* __restrict__ cell_off, const float4* __restrict__ pts, const float q[3], float best) {
-    const int lyz = ((z & 7) << 6) | ((y & 7) << 3);
-    const int base = ((z >> 3) * nbk[1] + (y >> 3)) * nbk[0];
-    const int bxa = xa >> 3, bxb = xb >> 3;
-    const int occ_a = block_table[base + bxa];
-    const int occ_b = bxb != bxa ? block_table[base + bxb] : -1;
-    int b0 = 0, e0 = 0, b1 = 0, e1 = 0;
-    if (occ_a >= 0) {
-        const int* off = cell_off + (size_t)occ_a * (kFitBlockCells + 1);
-        b0 = off[lyz | (xa & 7)];
-        e0 = off[(lyz | (bxb != bxa ? 7 : (xb & 7))) + 1];
-    }
-    if (occ_b >= 0) {
-        const int* off = cell_off + (size_t)occ_b * (kFitBlockCells + 1);
-        b1 = off[lyz];
-        e1 = off[(lyz | (xb & 7)) + 1];
-    }
-    best = range_min(pts, b0, e0, q, best);
-    return range_min(pts, b1, e1, q, best);
-}
-
-// min over up to kFitCells cells of a ring cube (cell k0, k0 + kFitTeam, ...: one lane's share), each level of loads
-// (block table, cell offsets, points) issued for all of them before any is consumed
-#ifndef NDT_FIT_CELLS
-#define NDT_FIT_CELLS 2
-#endif
-constexpr int kFitCells = NDT_FIT_CELLS;
-__device__ __forceinline__ float cells_min(int k0, int ncell, int side, int ring, const int c[3], const int db[3], const int nbk[3],
-                                           const int* __restrict__ block_table, const int* __restrict__ cell_off,
-                                           const float4* __restrict__ pts, const float q[3], float best) {
-    int occ[kFitCells], lc[kFitCells], b[kFitCells], n[kFitCells];
-#pragma unroll
-    for (int i = 0; i < kFitCells; ++i) {
-        const int k = k0 + i * kFitTeam;
-        const int x = c[0] + k % side - ring, y = c[1] + (k / side) % side - ring, z = c[2] + k / (side * side) - ring;
-        const bool in = k < ncell && x >= 0 && y >= 0 && z >= 0 && x < db[0] && y < db[1] && z < db[2];
-        lc[i] = ((z & 7) << 6) | ((y & 7) << 3) | (x & 7);
-        occ[i] = in ? block_table[((z >> 3) * nbk[1] + (y >> 3)) * nbk[0] + (x >> 3)] : -1;
-    }
-    int tot = 0;
-#pragma unroll
-    for (int i = 0; i < kFitCells; ++i) {
-        b[i] = 0;
-        n[i] = 0;
-        if (occ[i] >= 0) {
-            const int* off = cell_off + (size_t)occ[i] * (kFitBlockCells + 1);
-            b[i] = off[lc[i]];
-            n[i] = off[lc[i] + 1] - b[i];
-        }
-        tot += n[i];
-    }
-    // the cells' point ranges walked as one sequence, NDT_FIT_RANGE_U loads in flight (the last point repeated past the end)
-    constexpr int U = NDT_FIT_RANGE_U;
-    for (int j = 0; j < tot; j += U) {
-        float4 p[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            int v = min(j + u, tot - 1);
-            int idx = 0;
-#pragma unroll
-            for (int i = 0; i < kFitCells; ++i) {
-                if (v >= 0 && v < n[i]) idx = b[i] + v;
-                v -= n[i];
-            }
-            p[u] = pts[idx];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) best = fminf(best, l2_simple(p[u], q));
-    }
-    return best;
-}
-
-// The per-workgroup (sum, count) partials are summed by the last workgroup to finish (ticket), in a fixed order
-// (thread-strided, then a fixed tree), and written straight to the caller's pinned result slots.
-// Six waves per SIMD: the search is latency bound (a wave's 4 queries wait on dependent gathers 70 % of the time) and
-// 80 VGPRs still need no scratch (C3: 82.8 vs 87.8 us at the default 5 waves; 8 waves spill 76 B/lane, 93 us).
-#ifndef NDT_FIT_WAVES
-#define NDT_FIT_WAVES 6
-#endif
-__global__ __launch_bounds__(kFitBlock) __attribute__((amdgpu_waves_per_eu(NDT_FIT_WAVES))) void k_fitness(const float4* __restrict__ src, int n, Mat4f Tm, const GridHeader* __restrict__ h,
-                                                    const int* __restrict__ block_table, const int* __restrict__ cell_off,
-                                                    const float4* __restrict__ fit_pts, double max_range, float* __restrict__ nn_d2,
-                                                    double* __restrict__ part_sum, int* __restrict__ part_cnt,
-                                                    unsigned* __restrict__ ticket, double* __restrict__ out_sum,
-                                                    long long* __restrict__ out_cnt) {
-    const float* T = Tm.m;
-    double sum = 0.0;
-    int cnt = 0;
-    const bool empty = h->empty != 0 || h->n_leaves == 0;
-    const int db[3] = {h->div_b[0], h->div_b[1], h->div_b[2]};
-    const int nbk[3] = {h->nblk[0], h->nblk[1], h->nblk[2]};
-    const float cell = h->leaf[0];
-    const int t = threadIdx.x % kFitTeam;
-    const int teams = kFitBlock / kFitTeam;
-    for (int i = blockIdx.x * teams + threadIdx.x / kFitTeam; i < n; i += gridDim.x * teams) {
-        const float4 p = src[i];
-        float q[3];
-        q[0] = T[0] * p.x + T[4] * p.y + T[8] * p.z + T[12];
-        q[1] = T[1] * p.x + T[5] * p.y + T[9] * p.z + T[13];
-        q[2] = T[2] * p.x + T[6] * p.y + T[10] * p.z + T[14];
-        float best = INFINITY;
-        if (!empty) {
-            int c[3];
-            for (int a = 0; a < 3; ++a) c[a] = (int)(floorf(q[a] * h->inv_leaf[a]) - (float)h->min_b[a]);
-            const float slack = 1e-4f * cell + 4e-7f * (fabsf(q[0]) + fabsf(q[1]) + fabsf(q[2]));
-            int r0 = 0, rmax = 0;
-            for (int a = 0; a < 3; ++a) {
-                const int out = c[a] < 0 ? -c[a] : (c[a] >= db[a] ? c[a] - db[a] + 1 : 0);
-                r0 = max(r0, out);
-                rmax = max(rmax, max(c[a], db[a] - 1 - c[a]));
-            }
-            rmax = max(rmax, r0);
-            // distance from the query to the nearest face of its own cell
-            float face = cell;
-            for (int a = 0; a < 3; ++a) {
-                const float lo = (float)(c[a] + h->min_b[a]) * h->leaf[a];
-                face = fminf(face, fminf(fmaxf(q[a] - lo, 0.f), fmaxf(lo + h->leaf[a] - q[a], 0.f)));
-            }
-            bool done = false;
-            // ---- phase 1: the cubes of radius 1 (9 x-rows) and 2 (25 x-rows)
-            if (r0 <= 2) {
-                for (int ring = 1; ring <= 2 && !done; ++ring) {
-                    const int side = 2 * ring + 1;
-                    // one cell per lane of the team per step (x-rows per lane measured slower: 111 vs 95 us on C3), a
-                    // lane's cells NDT_FIT_CELLS at a time: their table, offset and point loads issued together
-                    const int ncell = side * side * side;
-                    for (int k0 = t; k0 < ncell; k0 += kFitCells * kFitTeam)
-                        best = cells_min(k0, ncell, side, ring, c, db, nbk, block_table, cell_off, fit_pts, q, best);
-                    best = team_min(best);
-                    // every unvisited point lies outside the cube of radius `ring` around the query cell: at least the
-                    // query's distance to the nearest cube face away (binning round-off inside the slack)
-                    const float bound = fmaxf(0.f, face + (float)ring * cell - slack);
-                    done = best <= bound * bound || ring >= rmax;
-                }
-            }
-            // ---- phase 2: block shells, each candidate block's points split over the team
-            if (!done) {
-                int cb[3], b0 = 0, bmax = 0;
-                for (int a = 0; a < 3; ++a) {
-                    cb[a] = c[a] >> 3;  // arithmetic shift: floor for cells left of the grid
-                    const int out = cb[a] < 0 ? -cb[a] : (cb[a] >= nbk[a] ? cb[a] - nbk[a] + 1 : 0);
-                    b0 = max(b0, out);
-                    bmax = max(bmax, max(cb[a], nbk[a] - 1 - cb[a]));
-                }
-                bmax = max(bmax, b0);
-                auto visit_block = [&](int x, int y, int z) {
-                    const int occ = block_table[((z * nbk[1] + y) * nbk[0]) + x];
-                    if (occ < 0) return;
-                    // lower bound: per-axis cell gap between the query cell and the block's cells
-                    const int bx[3] = {x, y, z};
-                    float lb = 0.f;
-                    for (int a = 0; a < 3; ++a) {
-                        const int lo = bx[a] * 8, hi = lo + 7;
-                        const int gap = c[a] < lo ? lo - c[a] - 1 : (c[a] > hi ? c[a] - hi - 1 : 0);
-                        const float g = fmaxf(0.f, (float)gap * cell - slack);
-                        lb += g * g;
-                    }
-                    if (lb >= best) return;  // best is team-uniform here
-                    const int* off = cell_off + (size_t)occ * (kFitBlockCells + 1);
-                    const int e = off[kFitBlockCells];
-                    // a block holds up to hundreds of points: eight loads in flight per lane (clamped repeats are
-                    // harmless for a minimum), not one round trip per point
-                    for (int j = off[0] + t; j < e; j += kFitP2 * kFitTeam) {
-                        float4 p[kFitP2];
-#pragma unroll
-                        for (int u = 0; u < kFitP2; ++u) p[u] = fit_pts[min(j + u * kFitTeam, e - 1)];
-#pragma unroll
-                        for (int u = 0; u < kFitP2; ++u) best = fminf(best, l2_simple(p[u], q));
-                    }
-                    best = team_min(best);
-                };
-                for (int r = b0; r <= bmax; ++r) {
-                    const int lo2 = max(cb[2] - r, 0), hi2 = min(cb[2] + r, nbk[2] - 1);
-                    const int lo1 = max(cb[1] - r, 0), hi1 = min(cb[1] + r, nbk[1] - 1);
-                    const int lo0 = max(cb[0] - r, 0), hi0 = min(cb[0] + r, nbk[0] - 1);
-                    for (int z = lo2; z <= hi2; ++z)
-                        for (int y = lo1; y <= hi1; ++y) {
-                            if (abs(z - cb[2]) == r || abs(y - cb[1]) == r) {
-                                for (int x = lo0; x <= hi0; ++x) visit_block(x, y, z);
-                            } else {
-                                if (cb[0] - r >= 0) visit_block(cb[0] - r, y, z);
-                                if (r > 0 && cb[0] + r <= nbk[0] - 1) visit_block(cb[0] + r, y, z);
-                            }
-                        }
-                    const float bound = fmaxf(0.f, (float)(8 * r) * cell - slack);
-                    if (best <= bound * bound) break;
-                }
-            }
-        }
-        if (t == 0) {
-            nn_d2[i] = best;
-            if (best != INFINITY && (double)best <= max_range) { sum += (double)best; ++cnt; }
-        }
-    }
-    // (sum, count): workgroup tree -> per-workgroup partial; the last workgroup of each group of kFitGroup sums its
-    // group's partials (one load per thread, fixed tree) into a group partial; the last group's reducer sums the
-    // group partials (fixed tree) into the caller's pinned result slots.  Hand-offs as in the pass epilogue (recipe
-    // R1): partials stored write-through (sc1) and drained before the ticket, the ticket taker acquires — an
-    // agent-scope release fence would write back the L2 in each of thousands of workgroups.  One counter per group
-    // (own cache line): thousands of increments of one word serialise at its L2 channel.
-    __shared__ double s_sum[kFitBlock];
-    __shared__ long long s_cnt[kFitBlock];
-    __shared__ int s_role;
-    auto tree = [&](double v, long long k) {
-        s_sum[threadIdx.x] = v;
-        s_cnt[threadIdx.x] = k;
-        __syncthreads();
-        for (int off = kFitBlock / 2; off > 0; off >>= 1) {
-            if ((int)threadIdx.x < off) { s_sum[threadIdx.x] += s_sum[threadIdx.x + off]; s_cnt[threadIdx.x] += s_cnt[threadIdx.x + off]; }
-            __syncthreads();
-        }
-    };
-    tree(sum, cnt);
-    const int nb = gridDim.x;
-    const int g = blockIdx.x / kFitGroup, ng = (nb + kFitGroup - 1) / kFitGroup;
-    const int g0 = g * kFitGroup, gsize = min(kFitGroup, nb - g0);
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(part_sum + blockIdx.x, s_sum[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(part_cnt + blockIdx.x, (int)s_cnt[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_role = __hip_atomic_fetch_add(&ticket[kFitTicketStride * (1 + g)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-                 (unsigned)gsize - 1;
-    }
-    __syncthreads();
-    if (!s_role) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    {
-        const int t = threadIdx.x;
-        tree(t < gsize ? part_sum[g0 + t] : 0.0, t < gsize ? (long long)part_cnt[g0 + t] : 0ll);
-    }
-    if (threadIdx.x == 0) {
-        ticket[kFitTicketStride * (1 + g)] = 0u;
-        __hip_atomic_store(part_sum + nb + g, s_sum[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(part_cnt + nb + g, (int)s_cnt[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_role = __hip_atomic_fetch_add(&ticket[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)ng - 1 ? 2 : 0;
-    }
-    __syncthreads();
-    if (s_role != 2) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    {
-        // more groups than threads: each thread first sums its strided share in ascending order (fixed order)
-        double v = 0.0;
-        long long k = 0;
-        for (int t = threadIdx.x; t < ng; t += kFitBlock) { v += part_sum[nb + t]; k += part_cnt[nb + t]; }
-        tree(v, k);
-    }
-    if (threadIdx.x == 0) {
-        // pinned host slots: system-scope stores; a count of -1 reports an index whose sort hit the look-back time limit
-        // (the header's error flag: the decoupled look-backs rely on each XCD dispatching its workgroups in order)
-        __hip_atomic_store(out_sum, s_sum[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(out_cnt, h->pad[0] ? -1ll : (long long)s_cnt[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        ticket[0] = 0u;
-    }
-}
-
-
 }  // namespace ndt
 
 #ifdef NDT_SORT_STAMPS
