@@ -88,7 +88,7 @@ static void check_pass(const PassShape& s, int which) {
         const long long max_cloud = (long long)s.M / std::max(1, s.min_points_per_voxel) + 1;
         if (ppt == 2) CHECK(max_cloud < (1ll << 22) && s.ppt == 2 && s.search != S_DIRECT26 && tiles >= 2, fmt, ARGS);
         if (s.search == S_DIRECT26) CHECK(ppt == 1 && !one && block == kBlock, fmt, ARGS);
-        CHECK(one == ((direct_one_tile(s) || grid_one_tile(s)) ? 1 : 0), fmt, ARGS);
+        CHECK(one == (grid_one_tile(s) ? 1 : 0), fmt, ARGS);
         if (grid_one_tile(s)) CHECK(nb == (n + 255) / 256 && ppb == 256 && s.ppt == 3, fmt, ARGS);
     }
     if (which == 1) CHECK(nb <= s.n_cu && o[6] == 0 && o[7] == 0, fmt, ARGS);

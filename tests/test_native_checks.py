@@ -27,13 +27,17 @@ def test_angle_table_entries_bit_exact(tmp_path):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
 def test_packed_pair_math_bit_exact(tmp_path):
     """pair_pk (the derivative pass's pair arithmetic as packed f32 pairs, ndt_pair.h) == pair_f32 (one f32 operation per
-    reference operation, ndt_omp_impl.hpp:491-548) on 400 k random pairs, with and without the Hessian."""
+    reference operation, ndt_omp_impl.hpp:491-548) on 400 k random pairs, with and without the Hessian; and the predicated
+    form the pass kernels call, pair_pk_terms<true>: equal to pair_f32 with valid = true, every sum untouched bit for bit
+    with valid = false (the program itself fails unless >= 1 % of the pairs are rejected and >= 50 % accepted)."""
     exe = tmp_path / "ppc"
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", str(exe),
                     os.path.join(HERE, "native", "pair_pk_check.cpp")], check=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "mismatched: 0" in out.stdout
+    assert "predicated differ: 0" in out.stdout
+    assert "masked changed: 0" in out.stdout
 
 def _quadmath_ok(tmp_path) -> bool:
     src = tmp_path / "q.cpp"

@@ -15,11 +15,11 @@ using namespace ndt;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
 constexpr int B = 768, NW = B / 64;
-constexpr int kPieces = 9;
+constexpr int kPieces = 7;
 
 __device__ __forceinline__ unsigned long long now() { return __builtin_amdgcn_s_memtime(); }
 
-// An instrumented copy of tail_control's fast path 3 (ndt_control.h): s_memtime stamps per wave into ts[]
+// An instrumented copy of tail_control's fast path (ndt_control.h): s_memtime stamps per wave into ts[]
 // [0] start, wave 0: [1] LU done [2] step regs [3] sincos [4] state stored [5] T; wave 1: [6] record [7] state machine
 // [8] step regs [9] sincos [10] entries; [11] after the closing barrier
 __device__ __noinline__ void fast3_stamped(AlignState& s_st, const double* red, PassRecordDev* hist, unsigned long long* tsl) {
@@ -108,9 +108,8 @@ __global__ __launch_bounds__(B) void k_tail_bench(const AlignState* __restrict__
     __shared__ AlignState s_st;
     __shared__ double red[kNumAcc];
     __shared__ double s_dp[6];
-    __shared__ double s_sc[12];
     const int t = threadIdx.x, wv = t >> 6;
-    unsigned long long acc[kPieces] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long acc[kPieces] = {0, 0, 0, 0, 0, 0, 0};
     __shared__ unsigned long long tsl[12];
     unsigned long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     constexpr int kWords = sizeof(AlignState) / 8;
@@ -144,51 +143,35 @@ __global__ __launch_bounds__(B) void k_tail_bench(const AlignState* __restrict__
         lds_barrier();
         t1 = now();
         acc[3] += t1 - t0;
-        // [4] the sin / cos wave (wave 0)
+        // [4] the sin / cos, T and the tables as the slow path runs them
         t0 = now();
-        if (wv == 0) pass_sincos_wave(&s_st, s_sc);
-        lds_barrier();
+        prepare_pass_parallel<NW>(&s_st);
         t1 = now();
         acc[4] += t1 - t0;
-        // [5] T + tables
-        t0 = now();
-        pass_tables<NW>(&s_st, s_sc);
-        t1 = now();
-        acc[5] += t1 - t0;
 
         // [6] the whole tail_control (as the kernels run it), from the pristine state again
         for (int k = t; k < kWords; k += B) reinterpret_cast<unsigned long long*>(&s_st)[k] = reinterpret_cast<const unsigned long long*>(st0)[k];
         lds_barrier();
         t0 = now();
-        tail_control<NW, 1>(s_st, red, hist, 0, nullptr);
+        tail_control<NW>(s_st, red, hist, 0, nullptr);
         lds_barrier();
         t1 = now();
         acc[6] += t1 - t0;
         if (r == reps - 1)
             for (int k = t; k < kWords; k += B) reinterpret_cast<unsigned long long*>(&st_out[0])[k] = reinterpret_cast<unsigned long long*>(&s_st)[k];
-        // [8] tail_control with fast path 3
-        for (int k = t; k < kWords; k += B) reinterpret_cast<unsigned long long*>(&s_st)[k] = reinterpret_cast<const unsigned long long*>(st0)[k];
-        lds_barrier();
-        t0 = now();
-        tail_control<NW, 3>(s_st, red, hist, 0, nullptr);
-        lds_barrier();
-        t1 = now();
-        acc[8] += t1 - t0;
-        if (r == reps - 1)
-            for (int k = t; k < kWords; k += B) reinterpret_cast<unsigned long long*>(&st_out[1])[k] = reinterpret_cast<unsigned long long*>(&s_st)[k];
-        // the instrumented fast path 3
+        // the instrumented fast path
         for (int k = t; k < kWords; k += B) reinterpret_cast<unsigned long long*>(&s_st)[k] = reinterpret_cast<const unsigned long long*>(st0)[k];
         lds_barrier();
         fast3_stamped(s_st, red, hist, tsl);
         lds_barrier();
         if (t == 0)
             for (int k = 1; k < 12; ++k) tacc[k] += tsl[k] - tsl[0];
-        // [7] an empty barrier pair (the measurement's own overhead)
+        // [5] an empty barrier pair (the measurement's own overhead)
         t0 = now();
         lds_barrier();
         lds_barrier();
         t1 = now();
-        acc[7] += t1 - t0;
+        acc[5] += t1 - t0;
         if (t == 0) sink[1] += s_st.x_t[0] + s_st.T[0] + s_st.jang[1][1];
     }
     if (t == 0) {
@@ -229,7 +212,7 @@ int main(int argc, char** argv) {
     red[43] = 380000.0;
     AlignState* d_st; AlignState* d_st_out; double* d_red; unsigned long long* d_out; double* d_sink; PassRecordDev* d_hist;
     CK(hipMalloc(&d_st, sizeof(st))); CK(hipMalloc(&d_red, sizeof(red))); CK(hipMalloc(&d_out, (kPieces + 12) * 8));
-    CK(hipMalloc(&d_sink, 16)); CK(hipMalloc(&d_hist, sizeof(PassRecordDev))); CK(hipMalloc(&d_st_out, 2 * sizeof(AlignState)));
+    CK(hipMalloc(&d_sink, 16)); CK(hipMalloc(&d_hist, sizeof(PassRecordDev))); CK(hipMalloc(&d_st_out, sizeof(AlignState)));
     CK(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice)); CK(hipMemcpy(d_red, red, sizeof(red), hipMemcpyHostToDevice));
     CK(hipMemset(d_sink, 0, 16));
     hipLaunchKernelGGL(k_tail_bench, dim3(1), dim3(B), 0, 0, d_st, d_red, 4, d_out, d_sink, d_hist, d_st_out);  // warm-up
@@ -239,22 +222,20 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(out, d_out, sizeof(out), hipMemcpyDeviceToHost));
     int clk_khz = 0;
     CK(hipDeviceGetAttribute(&clk_khz, hipDeviceAttributeClockRate, 0));
-    const char* names[kPieces] = {"lu6_solve_rows", "control_record_wave", "control_step", "newton_after_solve", "pass_sincos_wave",
-                                  "pass_tables", "tail_control (whole)", "two empty barriers", "tail_control fast 3"};
+    const char* names[kPieces] = {"lu6_solve_rows", "control_record_wave", "control_step", "newton_after_solve", "prepare_pass_parallel",
+                                  "two empty barriers", "tail_control (whole)"};
     printf("shader clock %d MHz, %d reps; cycles (us at that clock) per call incl. one barrier:\n", clk_khz / 1000, reps);
     for (int k = 0; k < kPieces; ++k)
         printf("  %-22s %8.0f cycles %7.3f us\n", names[k], (double)out[k] / reps, (double)out[k] / reps / (clk_khz / 1000.0));
     const char* tn[12] = {"", "w0 LU done", "w0 step regs", "w0 sincos", "w0 state stored", "w0 T", "w1 record", "w1 state machine",
                           "w1 step regs", "w1 sincos", "w1 entries", "closing barrier"};
-    printf("instrumented fast path 3 (cycles from its start):\n");
+    printf("instrumented fast path (cycles from its start):\n");
     for (int k = 1; k < 12; ++k) printf("  %-18s %8.0f\n", tn[k], (double)out[kPieces + k] / reps);
     double sk[2];
     CK(hipMemcpy(sk, d_sink, 16, hipMemcpyDeviceToHost));
     printf("sink %.1f\n", sk[0]);
-    AlignState so[2];
-    CK(hipMemcpy(so, d_st_out, sizeof(so), hipMemcpyDeviceToHost));
-    const bool same = std::memcmp(&so[0], &so[1], sizeof(AlignState)) == 0;
-    printf("fast 1 and fast 3 leave %s states (pending %d/%d, x_t[5] %.17g / %.17g, T[0] %.9g / %.9g)\n", same ? "bitwise identical" : "DIFFERENT",
-           so[0].pending, so[1].pending, so[0].x_t[5], so[1].x_t[5], so[0].T[0], so[1].T[0]);
-    return same ? 0 : 1;
+    AlignState so;
+    CK(hipMemcpy(&so, d_st_out, sizeof(so), hipMemcpyDeviceToHost));
+    printf("tail_control leaves pending %d, x_t[5] %.17g, T[0] %.9g\n", so.pending, so.x_t[5], so.T[0]);
+    return 0;
 }

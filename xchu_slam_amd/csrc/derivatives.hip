@@ -8,7 +8,8 @@
 // the point is transformed on the fly from the original cloud (no transformed-cloud round trip through
 // HBM), voxel neighbours come from an open-addressing hash probe, each (point, voxel) pair reads one
 // 64 B VoxelRec, per-pair math is f32 exactly as the reference (its dense 4x6/24x6 products restated
-// sparsely: the skipped terms are exact zeros), and the 43 sums are accumulated in f64 per thread,
+// sparsely: the skipped terms are exact zeros), and the 43 sums are accumulated in f64 per thread (the
+// direct passes: 22 per lane, the two halves of a wave each keeping one half of the terms, SplitSink),
 // reduced by a fixed wave butterfly + LDS into per-workgroup partials.  No atomics => bitwise
 // run-to-run determinism.  Memory-bound gather + reduction, no MFMA.
 #include "ndt_control.h"
@@ -23,14 +24,8 @@ __device__ __forceinline__ void stage_exp_tab(double* s_exp) {
     if (threadIdx.x < kExpTabLen) s_exp[threadIdx.x] = __longlong_as_double((long long)c_exp_tab[threadIdx.x]);
 }
 
-// Split accumulation (ndt_device.h): a lane keeps 22 f64 sums instead of 44 (88 -> 44 VGPRs), every pair's terms exchanged
-// across the half-waves as they are produced (22 v_permlane32_swap per pair); NDT_SPLIT_ACC=0 (ndt_types.h): every lane
-// keeps all 44 sums.
-constexpr int kBodyAcc = NDT_SPLIT_ACC ? kSplitAcc : kNumAcc;
-// record register sets of the pair loop: 2 (one gather in flight behind a pair's math) or 3 (two)
-#ifndef NDT_REC_SETS
-#define NDT_REC_SETS 2
-#endif
+// Split accumulation (ndt_device.h): a lane keeps kSplitAcc = 22 f64 sums instead of 44 (88 -> 44 VGPRs), every pair's
+// terms exchanged across the half-waves as they are produced (22 v_permlane32_swap per pair).
 
 // The pair sink of split accumulation.  put(k, lo, hi): this lane's low term k and high term k; after the swap lanes 0-31
 // hold the low term k of their own pair and of lane + 32's, lanes 32-63 the high term k of lane - 32's pair and of their
@@ -81,10 +76,8 @@ struct PointTerms {
 __device__ __forceinline__ void load_point_terms(const float4 p, const AlignState* __restrict__ st, PointTerms& t, bool hess) {
     const float* T = st->T;
     t.x[0] = p.x; t.x[1] = p.y; t.x[2] = p.z;
-    // pcl::transformPointCloud: ((m0*x + m1*y) + m2*z) + m3, f32
-    t.xt[0] = T[0] * p.x + T[4] * p.y + T[8] * p.z + T[12];
-    t.xt[1] = T[1] * p.x + T[5] * p.y + T[9] * p.z + T[13];
-    t.xt[2] = T[2] * p.x + T[6] * p.y + T[10] * p.z + T[14];
+    const float3 xt = transform_point(T, p.x, p.y, p.z);
+    t.xt[0] = xt.x; t.xt[1] = xt.y; t.xt[2] = xt.z;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         float acc = st->jang[r][0] * p.x;
@@ -106,8 +99,7 @@ __device__ __forceinline__ void load_point_terms(const float4 p, const AlignStat
 // computePointDerivatives terms of one source point (ndt_omp_impl.hpp:448-488, f32): the reference evaluates
 // them for every (point, voxel) pair; they depend on the point only, so the pass computes them once per point
 // into LDS and every pair of the point reads the same values.
-// Stored in the order the pair math reads it: natural (xj[8], xh[15], pad) for pair_f32, or pk_terms' f32 pairs for
-// pair_pk (NDT_PACKED_PAIR, ndt_pair.h).
+// Stored in the order the pair math reads it: pk_terms' f32 pairs (ndt_pair.h).
 struct __align__(16) PointDeriv {
     float v[24];
 };
@@ -117,7 +109,6 @@ static_assert(kPkTerms == 24, "pk_terms fill a PointDeriv");
 // tab: the f32 angle tables of the pass, j_ang (8 x 4) followed by h_ang (16 x 4) as in AlignState, read from LDS
 // (k_pass_lead's staged state, k_pass_direct's staged copy): uniform-address broadcasts instead of a chain of scalar
 // loads per tile
-template <bool PACKED>
 __device__ __forceinline__ void point_deriv(const float4 p, const float* __restrict__ tab, PointDeriv& d, bool hess) {
     float xj[8], xh[15];
 #pragma unroll
@@ -137,15 +128,7 @@ __device__ __forceinline__ void point_deriv(const float4 p, const float* __restr
         }
         xh[r] = acc;
     }
-    if (PACKED) {
-        pk_terms(xj, xh, d.v);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) d.v[r] = xj[r];
-#pragma unroll
-        for (int r = 0; r < 15; ++r) d.v[8 + r] = xh[r];
-        d.v[23] = 0.f;
-    }
+    pk_terms(xj, xh, d.v);
 }
 static_assert(offsetof(AlignState, hang) == offsetof(AlignState, jang) + 32 * sizeof(float), "h_ang follows j_ang");
 
@@ -177,13 +160,6 @@ __device__ __forceinline__ RecView rec_view(const RecRaw& r) {
 }
 static_assert(offsetof(VoxelRec, icov) == 24 && offsetof(VoxelRec, npts) == 60, "RecRaw decode assumes the VoxelRec layout");
 
-// pair_f32 operand view: transformed point + the point's derivative record (both from LDS)
-struct PairPoint {
-    float xt[3];
-    const float* xj;
-    const float* xh;
-};
-
 // A (point, voxel) pair of a tile in LDS: int2 (tile-local point, cloud index), or packed into one word (cloud index << 10
 // | tile-local point) where a tile holds two points per thread — the pair list then takes half the LDS, so that two
 // workgroups still fit a CU (the host packs only when every cloud index is below 2^22).
@@ -201,18 +177,10 @@ template <> struct PairSlot<2> {
     __device__ static int voxel(T s) { return (int)(s >> 10); }
 };
 
-#ifndef NDT_OWN_FIRST
-#define NDT_OWN_FIRST 1
-#endif
-// A/B switches of the leading-tail kernel's stretch between the control step and the body (profiles/r08_pass_header/AB.md):
-// 1 = partials_pending set in the state word workgroup 0 writes out (0: in LDS, behind a barrier of its own); 1 = the grid
-// header's lines touched at kernel start
-#ifndef NDT_LEAD_FLAG_PATCH
-#define NDT_LEAD_FLAG_PATCH 1
-#endif
-#ifndef NDT_LEAD_WARM
-#define NDT_LEAD_WARM 1
-#endif
+// probes per point of a direct search: DIRECT7's centre and six face neighbours, DIRECT26's 26 cells, DIRECT1's own cell
+__host__ __device__ constexpr int search_nrel(int search) { return search == S_DIRECT26 ? 26 : (search == S_DIRECT1 ? 1 : 7); }
+// half h of the neighbour-cache entry (two int4) that matches no cell: halo cells are >= 0, a point far from the grid has -1
+__device__ __forceinline__ int4 nbr_none(int h) { return make_int4(h == 0 ? -2 : 0, 0, 0, 0); }
 // a wave-uniform double moved to SGPRs (its two halves read from the first active lane)
 __device__ __forceinline__ double uniform_d(double x) {
     const long long b = __double_as_longlong(x);
@@ -243,8 +211,8 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
                                                  typename PairSlot<PPT>::T* s_pair, int* s_scan, const float* __restrict__ tab,
                                                  const double* __restrict__ etab, int4* __restrict__ nbr) {
     using PS = PairSlot<PPT>;
-    constexpr int NREL = SEARCH == S_DIRECT26 ? 26 : (SEARCH == S_DIRECT1 ? 1 : 7);
-    constexpr bool kOwn = NDT_OWN_FIRST && PPT == 1 && NDT_SPLIT_ACC && NDT_REC_SETS != 3;
+    constexpr int NREL = search_nrel(SEARCH);
+    constexpr bool kOwn = PPT == 1;
     const bool hess = st->pass_kind == PASS_FULL;
     // the Gaussian constants are uniform: held in SGPRs through the pair loop (LDS-staged state reads land in VGPRs)
     const float gd2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)st->gauss_d2)));
@@ -271,10 +239,10 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
     // tiles of ppb (<= PPT * B) points: tile t of this workgroup covers [(blockIdx + t*grid) * ppb, +ppb); thread k holds
     // tile-local points k, k + B, ...  The next tile's points are loaded at the top of each tile (one HBM round trip
     // hidden behind this tile's work).
-    // PPRE false (k_pass_direct's second body instantiation, a hash grid): the first tile's points are loaded here, not
+    // PPRE false (both kernels' second body instantiation, a hash grid): the first tile's points are loaded here, not
     // taken from the caller's registers — the dense / hash dispatch is structured as then-block, flow, else-block, so a
     // value the else-body reads is live through the whole then-body (C5's kernel: 256 VGPRs + 8 B of scratch -> 253, none;
-    // C4 1980 -> 1998 pairs/s).  The leading-tail kernel keeps its points (C2 1261 vs 1247 scans/s the other way).
+    // C4 1980 -> 1998 pairs/s; the leading-tail kernel 168 -> 166 VGPRs).
     float4 p_cur[PPT];
 #pragma unroll
     for (int q = 0; q < PPT; ++q) {
@@ -319,11 +287,8 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
         float4 xt[PPT];
 #pragma unroll
         for (int q = 0; q < PPT; ++q) {
-            // pcl::transformPointCloud: ((m0*x + m1*y) + m2*z) + m3, f32
-            xt[q].x = T[0] * p[q].x + T[4] * p[q].y + T[8] * p[q].z + T[12];
-            xt[q].y = T[1] * p[q].x + T[5] * p[q].y + T[9] * p[q].z + T[13];
-            xt[q].z = T[2] * p[q].x + T[6] * p[q].y + T[10] * p[q].z + T[14];
-            xt[q].w = 0.f;
+            const float3 x3 = transform_point(T, p[q].x, p[q].y, p[q].z);
+            xt[q] = make_float4(x3.x, x3.y, x3.z, 0.f);
             // getNeighborhoodAtPoint: ijk = floor(p / leaf_size) (float division), bounds vs min_b/max_b
             const int i0 = (int)floorf(xt[q].x / leaf0), i1 = (int)floorf(xt[q].y / leaf1), i2 = (int)floorf(xt[q].z / leaf2);
             int ck = -1;
@@ -341,7 +306,7 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
                 }
             }
             if (!settled) {
-            constexpr bool kTriple = NDT_ROW_TRIPLE && DENSE && SEARCH == S_DIRECT7;
+            constexpr bool kTriple = DENSE && SEARCH == S_DIRECT7;
             if (kTriple) {
                 // DIRECT7 offsets 0, +x, -x are three consecutive cells of one grid row: one dwordx3 load for the three
                 // (a point whose row triple would leave the grid allocation loads them one by one)
@@ -405,7 +370,7 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
             const int li = (int)threadIdx.x + q * B;
             s_xt[li] = xt[q];
             PointDeriv pd;
-            point_deriv<NDT_PACKED_PAIR != 0>(p[q], tab, pd, hess);
+            point_deriv(p[q], tab, pd, hess);
             s_pd[li] = pd;
         }
         // own first pair (kOwn): a point's first neighbour in probe order stays with its thread — its record gather is
@@ -467,55 +432,16 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
         auto pair_at = [&](const typename PS::T pr, const RecRaw& raw, bool valid) {
             const int pt = PS::point(pr);
             const float4 x = s_xt[pt];
-#if NDT_SPLIT_ACC
             const float xt3[3] = {x.x, x.y, x.z};
             SplitSink sink{acc};
             pair_pk_terms<true>(xt3, s_pd[pt].v, rec_view(raw), gd2, d1, hess, etab, sink, valid);
-#elif NDT_PACKED_PAIR
-            (void)valid;
-            const float xt3[3] = {x.x, x.y, x.z};
-            pair_pk(xt3, s_pd[pt].v, rec_view(raw), gd2, d1, hess, acc, etab);
-#else
-            PairPoint t;
-            t.xt[0] = x.x; t.xt[1] = x.y; t.xt[2] = x.z;
-            t.xj = s_pd[pt].v;
-            t.xh = s_pd[pt].v + 8;
-            (void)valid;
-            pair_f32(t, rec_view(raw), gd2, d1, hess, acc, etab);
-#endif
         };
         // two register sets A / B: A's reload is issued right after A's math, B's load right before it, so one
         // record gather is always in flight behind the current pair's math and no record is ever copied.  Split
         // accumulation exchanges terms between lanes, so every lane of a wave runs every iteration its first lane runs
-        // (lanes past the tile's pairs compute a clamped pair and mask it out); otherwise each lane stops at its last pair.
-        constexpr bool kWaveLoop = NDT_SPLIT_ACC != 0;
+        // (lanes past the tile's pairs compute a clamped pair and mask it out).
         int j = threadIdx.x;
-        const int jw0 = kWaveLoop ? (int)(threadIdx.x & ~63u) : j;  // the loop's exit test: wave-uniform with split sums
-#if NDT_REC_SETS == 3
-        // three sets A / B / C: two record gathers in flight behind the current pair's math
-        if (jw0 < tot) {
-            auto pA = s_pair[min(j, tot - 1)];
-            RecRaw A = load_rec(recs, PS::voxel(pA));
-            auto pB = s_pair[min(j + B, tot - 1)];
-            RecRaw Bv = load_rec(recs, PS::voxel(pB));
-            for (int jw = jw0;;) {
-                const auto pC = s_pair[min(j + 2 * B, tot - 1)];
-                const RecRaw Cv = load_rec(recs, PS::voxel(pC));
-                pair_at(pA, A, j < tot);
-                if (jw + B >= tot) break;
-                pA = s_pair[min(j + 3 * B, tot - 1)];
-                A = load_rec(recs, PS::voxel(pA));
-                pair_at(pB, Bv, j + B < tot);
-                if (jw + 2 * B >= tot) break;
-                pB = s_pair[min(j + 4 * B, tot - 1)];
-                Bv = load_rec(recs, PS::voxel(pB));
-                pair_at(pC, Cv, j + 2 * B < tot);
-                if (jw + 3 * B >= tot) break;
-                j += 3 * B;
-                jw += 3 * B;
-            }
-        }
-#else
+        const int jw0 = (int)(threadIdx.x & ~63u);  // the loop's exit test is wave-uniform
         // the own pair's math (wave-uniform: a wave with no own pair skips it), behind the first compacted gather
         const bool wave_own = kOwn && __ballot(own) != 0;
         const auto own_slot = PS::pack(own ? (int)threadIdx.x : 0, 0);
@@ -540,7 +466,6 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
         } else if (wave_own) {
             pair_at(own_slot, own_rec, own);
         }
-#endif
         lds_barrier();
         NDT_BLK_STAMP(pidx, 3);
 #ifdef NDT_BODY_STAMPS
@@ -574,8 +499,8 @@ __device__ __forceinline__ void pass_direct_impl(const float4* __restrict__ src,
         const int li = (int)threadIdx.x + q * B, i_first = blockIdx.x * ppb + li;
         const bool on_first = li < ppb && i_first < n;
         p_first[q] = on_first ? src[i_first] : make_float4(0.f, 0.f, 0.f, 0.f);
-        e_first[q][0] = make_int4(-2, 0, 0, 0);
-        e_first[q][1] = make_int4(0, 0, 0, 0);
+        e_first[q][0] = nbr_none(0);
+        e_first[q][1] = nbr_none(1);
         if (nbr && on_first) {
             // the first tile's neighbour cache entries, read beside its points (used only from an align's second pass on)
             e_first[q][0] = nbr[2 * (size_t)i_first];
@@ -591,13 +516,13 @@ __device__ __forceinline__ void pass_direct_impl(const float4* __restrict__ src,
     if (pass_idx >= kMaxHistory) ts = nullptr;
     if (ts && stamp0) ts[kTsStride * pass_idx] = t_entry;
     __shared__ double red[NW * kNumAcc];
-    double acc[kBodyAcc];
+    double acc[kSplitAcc];
 #pragma unroll
-    for (int v = 0; v < kBodyAcc; ++v) acc[v] = 0.0;
+    for (int v = 0; v < kSplitAcc; ++v) acc[v] = 0.0;
     long long pairs = 0;
     NDT_BLK_STAMP(pass_idx, 0);
     // one set of LDS tiles shared by both grid flavours of the body
-    constexpr int NREL = SEARCH == S_DIRECT26 ? 26 : (SEARCH == S_DIRECT1 ? 1 : 7);
+    constexpr int NREL = search_nrel(SEARCH);
     __shared__ float4 s_xt[B * PPT];
     __shared__ PointDeriv s_pd[B * PPT];
     __shared__ typename PairSlot<PPT>::T s_pair[B * PPT * NREL];
@@ -615,18 +540,12 @@ __device__ __forceinline__ void pass_direct_impl(const float4* __restrict__ src,
         direct_pass_body<SEARCH, false, B, PPT, ONE_TILE, false>(src, n_pts, ppb, hdr, table, grid, recs, st, acc, pairs, pass_idx, p_first, e_first,
                                                 s_xt, s_pd, s_pair, s_scan, s_tab, s_exp, nbr);
     // the body only reads the state through the const view; only the last workgroup writes it (st_mut)
-#if NDT_SPLIT_ACC
     if (threadIdx.x == 32) acc[3] += (double)pairs;  // the high set's pair-count slot (split_hi_term(3) = 43)
     block_reduce_store_split<NW>(acc, red, partials + blockIdx.x, partial_stride(gridDim.x));
     // three-wave (one-tile) kernels reduce the partials two column pairs per lane and round trip: the four-pair loads do
     // not fit their registers
     const bool tail = pass_handoff<NW, ONE_TILE ? 2 : 4>(st_mut, partials, counter, red_out, hist, hist_cap, mode,
                                                           ts ? ts + kTsStride * pass_idx : nullptr);
-#else
-    acc[43] = threadIdx.x == 0 ? (double)pairs : 0.0;
-    const bool tail = pass_epilogue<NW>(acc, red, st_mut, partials, counter, red_out, hist, hist_cap, mode,
-                                         ts ? ts + kTsStride * pass_idx : nullptr);
-#endif
     if (ts && tail) {
         __syncthreads();
         if (threadIdx.x == 0) ts[kTsStride * pass_idx + 1] = __builtin_amdgcn_s_memrealtime();
@@ -670,19 +589,13 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
     const bool on_first = (int)threadIdx.x < ppb && i_first < n;
     const float4 p_first[1] = {on_first ? src[i_first] : make_float4(0.f, 0.f, 0.f, 0.f)};
     // the neighbour cache entries of this workgroup's points, read next to them (ahead of the Newton step)
-    int4 e_first[1][2] = {{make_int4(-2, 0, 0, 0), make_int4(0, 0, 0, 0)}};
+    int4 e_first[1][2] = {{nbr_none(0), nbr_none(1)}};
     if (nbr && on_first) {
         e_first[0][0] = nbr[2 * (size_t)i_first];
         e_first[0][1] = nbr[2 * (size_t)i_first + 1];
     }
     __shared__ AlignState s_st;
     __shared__ __align__(16) double s_exp[kExpTabLen];
-#ifndef NDT_LEAD_PRELOAD
-#define NDT_LEAD_PRELOAD 1
-#endif
-#ifndef NDT_LEAD_HASH_PPRE
-#define NDT_LEAD_HASH_PPRE 0
-#endif
     PartialsPre<NW, 2> pre;
     {
         // the exp table's and the state's words loaded together from clamped addresses (no branch around a load: a load
@@ -695,19 +608,17 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
         const unsigned long long b = gw[t + B < kWords ? t + B : 0];
         // the previous pass's first 256 partial columns, loaded behind the state (in flight while it is stored and
         // inspected; a kernel that consumes none discards them)
-        if (NDT_LEAD_PRELOAD) partials_preload<NW, 2>(part_in, gridDim.x, pre);
+        partials_preload<NW, 2>(part_in, gridDim.x, pre);
         if (t < kExpTabLen) s_exp[t] = __longlong_as_double((long long)ew);
         if (t < kWords) lw[t] = a;
         if (t + B < kWords) lw[t + B] = b;
-        if (NDT_LEAD_WARM) {
-            // one word of each of the grid header's three 64-byte lines the body reads (none of them a word it reads):
-            // the lines are in the scalar cache when the body's header loads come, behind the control step, where they
-            // are three dependent round trips (dense / hash dispatch, halo sizes, the rest)
-            const unsigned* w = reinterpret_cast<const unsigned*>(hdr);
-            const unsigned touch = w[offsetof(GridHeader, min_b) / 4 + 3] ^ w[offsetof(GridHeader, inv_leaf) / 4 + 3] ^
-                                   w[offsetof(GridHeader, n_points) / 4];
-            asm volatile("" ::"s"(touch));
-        }
+        // one word of each of the grid header's three 64-byte lines the body reads (none of them a word it reads): the
+        // lines are in the scalar cache when the body's header loads come, behind the control step, where they are three
+        // dependent round trips (dense / hash dispatch, halo sizes, the rest)
+        const unsigned* w = reinterpret_cast<const unsigned*>(hdr);
+        const unsigned touch = w[offsetof(GridHeader, min_b) / 4 + 3] ^ w[offsetof(GridHeader, inv_leaf) / 4 + 3] ^
+                               w[offsetof(GridHeader, n_points) / 4];
+        asm volatile("" ::"s"(touch));
     }
     lds_barrier();
     // profiling: this kernel's start is the start of its body's pass and the end of the pass whose partials it consumes
@@ -729,13 +640,11 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
         // two column pairs per lane and row: one round trip covers the 256 partial columns of a one-workgroup-per-CU
         // grid (four left half the loads predicated off; the non-zero terms are added in the same order either way):
         // C2 20.77 vs 21.10 us per pass, 1105 / 1107 vs 1089 / 1095 scans/s (same-box A/B)
-        if (NDT_LEAD_PRELOAD) reduce_partials_pre<NW, 2, 2>(part_in, gridDim.x, pre, red);
-        else reduce_partials_block<NW, 2>(part_in, gridDim.x, red);
+        reduce_partials_pre<NW, 2, 2>(part_in, gridDim.x, pre, red);
 #ifdef NDT_BODY_STAMPS
         t_reduced = __builtin_amdgcn_s_memrealtime();
 #endif
         tail_control<NW>(s_st, red, hist, blockIdx.x == 0 ? hist_cap : 0, nullptr);
-        if (!NDT_LEAD_FLAG_PATCH && threadIdx.x == 0) s_st.partials_pending = 0;
         lds_barrier();
     }
 #ifdef NDT_BODY_STAMPS
@@ -754,10 +663,6 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
     // partials_pending of the state this kernel leaves (1: its body's partials are to be consumed).  No thread of this
     // kernel reads it again, so workgroup 0 sets it in the word it writes out; set in LDS it took a workgroup barrier of its
     // own in every workgroup, between the control step and the body (C2 17.83 -> 17.70 us per pass, profiles/r08_pass_header)
-    if (!NDT_LEAD_FLAG_PATCH) {
-        if (threadIdx.x == 0 && body) s_st.partials_pending = 1;
-        lds_barrier();
-    }
     if (blockIdx.x == 0) {
         const unsigned long long* lw = reinterpret_cast<const unsigned long long*>(&s_st);
         unsigned long long* gw = reinterpret_cast<unsigned long long*>(st_out);
@@ -765,18 +670,18 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
         constexpr int kFlagShift = (offsetof(AlignState, partials_pending) % 8) * 8;
         for (int k = threadIdx.x; k < kWords; k += B) {
             unsigned long long w = lw[k];
-            if (NDT_LEAD_FLAG_PATCH && k == kFlagWord)
+            if (k == kFlagWord)
                 w = (w & ~(0xffffffffull << kFlagShift)) | ((unsigned long long)(body ? 1u : 0u) << kFlagShift);
             gw[k] = w;
         }
     }
     if (!body) return;
     __shared__ double redw[NW * kNumAcc];
-    double acc[kBodyAcc];
+    double acc[kSplitAcc];
 #pragma unroll
-    for (int v = 0; v < kBodyAcc; ++v) acc[v] = 0.0;
+    for (int v = 0; v < kSplitAcc; ++v) acc[v] = 0.0;
     long long pairs = 0;
-    constexpr int NREL = SEARCH == S_DIRECT26 ? 26 : (SEARCH == S_DIRECT1 ? 1 : 7);
+    constexpr int NREL = search_nrel(SEARCH);
     __shared__ float4 s_xt[B];
     __shared__ PointDeriv s_pd[B];
     __shared__ int2 s_pair[B * NREL];
@@ -788,18 +693,13 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
         direct_pass_body<SEARCH, true, B, 1, ONE_TILE>(src, n_pts, ppb, hdr, table, grid, recs, &s_st, acc, pairs, pidx, p_first, e_first, s_xt,
                                           s_pd, s_pair, s_scan, &s_st.jang[0][0], s_exp, nbr);
     else {
-        const int4 e_none[1][2] = {{make_int4(-2, 0, 0, 0), make_int4(0, 0, 0, 0)}};
-        direct_pass_body<SEARCH, false, B, 1, ONE_TILE, false, NDT_LEAD_HASH_PPRE != 0>(src, n_pts, ppb, hdr, table, grid, recs, &s_st, acc, pairs, pidx, p_first,
+        const int4 e_none[1][2] = {{nbr_none(0), nbr_none(1)}};
+        direct_pass_body<SEARCH, false, B, 1, ONE_TILE, false>(src, n_pts, ppb, hdr, table, grid, recs, &s_st, acc, pairs, pidx, p_first,
                                                                e_none, s_xt, s_pd, s_pair, s_scan, &s_st.jang[0][0], s_exp, nbr);
     }
-#if NDT_SPLIT_ACC
     if (threadIdx.x == 32) acc[3] += (double)pairs;
     block_reduce_store_split<NW>(acc, redw, part_out + blockIdx.x, partial_stride(gridDim.x));
     NDT_BLK_STAMP(pidx, 4);
-#else
-    acc[43] = threadIdx.x == 0 ? (double)pairs : 0.0;
-    block_reduce_store<kNumAcc, NW>(acc, redw, part_out + blockIdx.x, partial_stride(gridDim.x));
-#endif
 }
 #define NDT_LEAD_INST(S, ONE)                                                                                                   \
     template __global__ void k_pass_lead<S, ONE>(const float4*, int, int, const GridHeader*, const int2*, const int*, const VoxelRec*, \
@@ -1070,10 +970,8 @@ __global__ __launch_bounds__(kBlock) void k_score_radius(const float4* __restric
     const RadiusGrid rg = radius_grid(hdr, radius);
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n && !empty; i += gridDim.x * kBlock) {
         const float4 p = src[i];
-        float xt[3];
-        xt[0] = T[0] * p.x + T[4] * p.y + T[8] * p.z + T[12];
-        xt[1] = T[1] * p.x + T[5] * p.y + T[9] * p.z + T[13];
-        xt[2] = T[2] * p.x + T[6] * p.y + T[10] * p.z + T[14];
+        const float3 x3 = transform_point(T, p.x, p.y, p.z);
+        const float xt[3] = {x3.x, x3.y, x3.z};
         float cd[kMaxCand];
         int ci[kMaxCand];
         const int nc = radius_candidates(rg, xt, grid, table, cent, cd, ci);

@@ -2,13 +2,11 @@
 // source point over the target's NNIndex (built by the k_fit_* kernels of voxel_build.hip), the squared distances within
 // max_range summed.
 #include <hip/hip_runtime.h>
-#include "ndt_types.h"
+#include "ndt_device.h"
 #include "ndt_nnwalk.h"
 #include "ndt_kernels.h"
 
 namespace ndt {
-
-constexpr int kFitBlock = NDT_FIT_BLOCK;  // threads per k_fitness workgroup (ndt_types.h)
 
 // Exact nearest neighbour of each transformed source point (pcl::transformPointCloud in f32) over all target points, one
 // 16-lane team per query: nn_walk (ndt_nnwalk.h) with the minimum tracker.
@@ -16,10 +14,8 @@ constexpr int kFitBlock = NDT_FIT_BLOCK;  // threads per k_fitness workgroup (nd
 // (thread-strided, then a fixed tree), and written straight to the caller's pinned result slots.
 // Six waves per SIMD: the search is latency bound (a wave's 4 queries wait on dependent gathers 70 % of the time) and
 // 80 VGPRs still need no scratch (C3: 82.8 vs 87.8 us at the default 5 waves; 8 waves spill 76 B/lane, 93 us).
-#ifndef NDT_FIT_WAVES
-#define NDT_FIT_WAVES 6
-#endif
-__global__ __launch_bounds__(kFitBlock) __attribute__((amdgpu_waves_per_eu(NDT_FIT_WAVES))) void k_fitness(const float4* __restrict__ src, int n, Mat4f Tm, const GridHeader* __restrict__ h,
+constexpr int kFitWaves = 6;
+__global__ __launch_bounds__(kFitBlock) __attribute__((amdgpu_waves_per_eu(kFitWaves))) void k_fitness(const float4* __restrict__ src, int n, Mat4f Tm, const GridHeader* __restrict__ h,
                                                     const int* __restrict__ block_table, const int* __restrict__ cell_off,
                                                     const float4* __restrict__ fit_pts, double max_range, float* __restrict__ nn_d2,
                                                     double* __restrict__ part_sum, int* __restrict__ part_cnt,
@@ -36,10 +32,8 @@ __global__ __launch_bounds__(kFitBlock) __attribute__((amdgpu_waves_per_eu(NDT_F
     const int teams = kFitBlock / kNnTeam;
     for (int i = blockIdx.x * teams + threadIdx.x / kNnTeam; i < n; i += gridDim.x * teams) {
         const float4 p = src[i];
-        float q[3];
-        q[0] = T[0] * p.x + T[4] * p.y + T[8] * p.z + T[12];
-        q[1] = T[1] * p.x + T[5] * p.y + T[9] * p.z + T[13];
-        q[2] = T[2] * p.x + T[6] * p.y + T[10] * p.z + T[14];
+        const float3 x3 = transform_point(T, p.x, p.y, p.z);
+        const float q[3] = {x3.x, x3.y, x3.z};
         NnMin best = {INFINITY};
         if (!empty) nn_walk(q, t, h, db, nbk, cell, block_table, cell_off, fit_pts, best);
         if (t == 0) {

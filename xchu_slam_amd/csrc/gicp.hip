@@ -14,8 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <limits.h>
-#include "ndt_types.h"
-#include "ndt_linalg.h"
+#include "ndt_device.h"
 #include "ndt_gicp.h"
 #include "ndt_nnwalk.h"
 #include "ndt_lastwg.h"
@@ -222,18 +221,15 @@ __global__ __launch_bounds__(kGicpBlock) void k_gicp_pairs(const float4* __restr
     for (int i = blockIdx.x * kGicpTeams + threadIdx.x / kGicpTeam; i < n; i += gridDim.x * kGicpTeams) {
         const float4 p = src[i];
         // query = transformation_ * (guess * p), two f32 matrix-vector products
-        const float gx = ((G[0] * p.x + G[4] * p.y) + G[8] * p.z) + G[12];
-        const float gy = ((G[1] * p.x + G[5] * p.y) + G[9] * p.z) + G[13];
-        const float gz = ((G[2] * p.x + G[6] * p.y) + G[10] * p.z) + G[14];
-        const float q[3] = {((T[0] * gx + T[4] * gy) + T[8] * gz) + T[12], ((T[1] * gx + T[5] * gy) + T[9] * gz) + T[13],
-                            ((T[2] * gx + T[6] * gy) + T[10] * gz) + T[14]};
+        const float3 g3 = transform_point(G, p.x, p.y, p.z), q3 = transform_point(T, g3.x, g3.y, g3.z);
+        const float q[3] = {q3.x, q3.y, q3.z};
         NnArg a = {INFINITY, -1, INT_MAX, fit_idx};
         if (!empty) nn_walk(q, t, h, db, nbk, cell, block_table, cell_off, fit_pts, a);
         const bool keep = a.pos >= 0 && (double)a.d < corr2;  // strict, unlike ICP
         if (t == 0) {
             match[i] = keep ? a.orig : -1;
             nn_d2[i] = a.d;
-            gp[i] = make_float4(gx, gy, gz, 1.f);
+            gp[i] = make_float4(g3.x, g3.y, g3.z, 1.f);
             if (keep) {
                 ++cnt;
                 qt[i] = fit_pts[a.pos];
@@ -287,10 +283,8 @@ __global__ __launch_bounds__(kGicpBlock) void k_gicp_eval(const float4* __restri
     for (int i = blockIdx.x * kGicpBlock + threadIdx.x; i < n; i += gridDim.x * kGicpBlock) {
         if (match[i] < 0) continue;
         const float4 p = src[i], q = qt[i], g = gp[i];
-        const float px = ((T[0] * p.x + T[4] * p.y) + T[8] * p.z) + T[12];
-        const float py = ((T[1] * p.x + T[5] * p.y) + T[9] * p.z) + T[13];
-        const float pz = ((T[2] * p.x + T[6] * p.y) + T[10] * p.z) + T[14];
-        const double res[3] = {(double)(px - q.x), (double)(py - q.y), (double)(pz - q.z)};  // f32 differences widened
+        const float3 pt = transform_point(T, p.x, p.y, p.z);
+        const double res[3] = {(double)(pt.x - q.x), (double)(pt.y - q.y), (double)(pt.z - q.z)};  // f32 differences widened
         const double* m = M + (size_t)9 * i;
         double tmp[3];
 #pragma unroll

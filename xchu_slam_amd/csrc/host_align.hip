@@ -66,7 +66,6 @@ bool needs_radius(const ndt_params& p, bool mt_possible) { return !needs_direct(
 // The launch geometry (ndt_geom.h) of this ctx's source, target, params and options
 bool grid_one_tile(const ndt_ctx* c) { return grid_one_tile(pass_shape(c)); }
 bool pass_ppt2(const ndt_ctx* c) { return pass_ppt2(pass_shape(c)); }
-bool direct_one_tile(const ndt_ctx* c) { return direct_one_tile(pass_shape(c)); }
 bool lead_one_tile(const ndt_ctx* c) { return lead_one_tile(pass_shape(c)); }
 PassGeom direct_geom(const ndt_ctx* c, bool lead) { return direct_geom(pass_shape(c), lead); }
 
@@ -83,11 +82,11 @@ bool nbr_single_tile(const ndt_ctx* c, bool lead) {
 }
 // allocation: whichever chain (leading tail or not) the next align picks
 bool nbr_cache_wanted(const ndt_ctx* c) {
-    if (c->prm.search != NDT_DIRECT7 || !NDT_NBR_CACHE) return false;
+    if (c->prm.search != NDT_DIRECT7) return false;
     return nbr_single_tile(c, true) || nbr_single_tile(c, false);
 }
 int4* nbr_cache(ndt_ctx* c, int mode) {
-    if (mode != 0 || c->prm.search != NDT_DIRECT7 || !NDT_NBR_CACHE || !nbr_single_tile(c, c->lead != 0)) return nullptr;
+    if (mode != 0 || c->prm.search != NDT_DIRECT7 || !nbr_single_tile(c, c->lead != 0)) return nullptr;
     return c->nbr.cap >= 2 * (size_t)geom_points(std::max(1, c->N)) ? c->nbr.p : nullptr;
 }
 
@@ -95,7 +94,7 @@ void launch_pass(ndt_ctx* c, int mode) {
     const ndt_params& p = c->prm;
     if (!needs_direct(p)) return;
     const PassGeom g = direct_geom(c, false);
-    const bool ppt2 = pass_ppt2(c), one = direct_one_tile(c) || grid_one_tile(c);
+    const bool ppt2 = pass_ppt2(c), one = grid_one_tile(c);
     auto* kern = p.search == NDT_DIRECT26 ? k_pass_direct<S_DIRECT26, 1, false>
                  : p.search == NDT_DIRECT1
                      ? (ppt2 ? k_pass_direct<S_DIRECT1, 2, false> : (one ? k_pass_direct<S_DIRECT1, 1, true> : k_pass_direct<S_DIRECT1, 1, false>))
@@ -412,10 +411,7 @@ ndt_status collect_pass_times(ndt_ctx* c, int hist_before) {
 // Source order of this align (k_src_keys): points sorted by the target cell they fall into under the initial
 // transform, so that neighbouring lanes of a pass probe and gather neighbouring cells.  Clouds below 256 Ki points keep
 // their order: there the sort (~35 us) costs about what it saves (C2: 1.5 us per pass over 33 passes; C3: 2-4 passes).
-#ifndef NDT_ORDER_MIN_POINTS
-#define NDT_ORDER_MIN_POINTS 262144
-#endif
-constexpr int kOrderMinPoints = NDT_ORDER_MIN_POINTS;
+constexpr int kOrderMinPoints = 262144;
 constexpr int kLeadMaxPoints = 262144;  // leading-tail chains below this many source points (align_enqueue)
 ndt_status enqueue_source_order(ndt_ctx* c, const float T[16]) {
     c->pass_src = c->source.p;
@@ -661,12 +657,8 @@ ndt_status ndt_set_source_device(ndt_ctx* c, const float* d_xyz4, size_t n) {
     if (c->source.p != old) invalidate_graph(c);  // a new size alone keeps the chains (geom_points)
     // the copy is deferred: the next align does it in its k_align_init (one launch less), any other reader of the source
     // first (flush_source); stream order is unchanged (nothing between reads the ctx source)
-#ifndef NDT_DEFER_SOURCE
-#define NDT_DEFER_SOURCE 1
-#endif
     c->src_pend = n ? reinterpret_cast<const float4*>(d_xyz4) : nullptr;
     c->N = (int)n;
-    if (!NDT_DEFER_SOURCE) TRY(flush_source(c));
     c->has_source = true;
     ++c->src_gen;
     c->have_result = false;

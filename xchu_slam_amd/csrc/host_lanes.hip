@@ -191,8 +191,8 @@ static ndt_status fitness_enqueue(ndt_ctx* c, const float* T, double max_range, 
         HIPCHK(c, hipStreamWaitEvent(c->lanes.fit_stream.get(), c->lanes.ev_main_fit.get(), 0));
         // 16-lane team per query; the grid capped at 32 Ki workgroups (measured caps 8192 / 2048 / 1024 / 512 of 256-thread
         // workgroups: 89.4 / 85.9 / 90.7 / 128.9 us on C3)
-        constexpr int grid_cap = 8192 * (256 / NDT_FIT_BLOCK);
-        const int nb = std::max(1, std::min(ceil_div(N, NDT_FIT_BLOCK / NDT_FIT_TEAM), grid_cap));
+        constexpr int grid_cap = 8192 * (256 / kFitBlock);
+        const int nb = std::max(1, std::min(ceil_div(N, kFitBlock / kFitTeam), grid_cap));
         const int ngrp = ceil_div(nb, kFitGroup);
         TRY(ensure(c, c->fit_sum, nb + ngrp)); TRY(ensure(c, c->fit_cnt, nb + ngrp)); TRY(ensure(c, c->fit_d2, N));
         const size_t n_ticket = (size_t)kFitTicketStride * (1 + ngrp);
@@ -201,7 +201,7 @@ static ndt_status fitness_enqueue(ndt_ctx* c, const float* T, double max_range, 
             HIPCHK(c, hipMemsetAsync(c->fit_ticket.p, 0, c->fit_ticket.cap * sizeof(unsigned), c->lanes.fit_stream.get()));
         }
         // the last workgroup sums the partials and writes (sum, count) straight into the pinned result slots
-        hipLaunchKernelGGL(k_fitness, dim3(nb), dim3(NDT_FIT_BLOCK), 0, c->lanes.fit_stream.get(), src, N, Tm, c->fit_ix.hdr.p, c->fit_ix.blk.p,
+        hipLaunchKernelGGL(k_fitness, dim3(nb), dim3(kFitBlock), 0, c->lanes.fit_stream.get(), src, N, Tm, c->fit_ix.hdr.p, c->fit_ix.blk.p,
                            c->fit_ix.off.p, c->fit_ix.pts.p, max_range, c->fit_d2.p, c->fit_sum.p, c->fit_cnt.p, c->fit_ticket.p,
                            &c->h_async->fit_sum, &c->h_async->fit_cnt);
         HIPCHK(c, hipGetLastError());

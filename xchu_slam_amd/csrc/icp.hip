@@ -15,8 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <limits.h>
-#include "ndt_types.h"
-#include "ndt_linalg.h"
+#include "ndt_device.h"
 #include "ndt_icp.h"
 #include "ndt_nnwalk.h"
 #include "ndt_lastwg.h"
@@ -99,13 +98,7 @@ __device__ void icp_control(const double* S, IcpState* st, IcpRecordDev* hist) {
 
 }  // namespace
 
-// NDT_ICP_WAVES (A/B builds): waves per SIMD the register allocation is held to; unset = the compiler's choice
-#ifdef NDT_ICP_WAVES
-#define NDT_ICP_OCC __attribute__((amdgpu_waves_per_eu(NDT_ICP_WAVES)))
-#else
-#define NDT_ICP_OCC
-#endif
-__global__ __launch_bounds__(kIcpBlock) NDT_ICP_OCC void k_icp_pass(float4* __restrict__ X, int n, IcpState* __restrict__ st,
+__global__ __launch_bounds__(kIcpBlock) void k_icp_pass(float4* __restrict__ X, int n, IcpState* __restrict__ st,
                                                         const GridHeader* __restrict__ h, const int* __restrict__ block_table,
                                                         const int* __restrict__ cell_off, const float4* __restrict__ fit_pts,
                                                         const int* __restrict__ fit_idx, int* __restrict__ match,
@@ -131,10 +124,8 @@ __global__ __launch_bounds__(kIcpBlock) NDT_ICP_OCC void k_icp_pass(float4* __re
     for (int i = blockIdx.x * kIcpTeams + threadIdx.x / kIcpTeam; i < n; i += gridDim.x * kIcpTeams) {
         float4 p = X[i];
         if (apply) {
-            const float x = T[0] * p.x + T[4] * p.y + T[8] * p.z + T[12];
-            const float y = T[1] * p.x + T[5] * p.y + T[9] * p.z + T[13];
-            const float z = T[2] * p.x + T[6] * p.y + T[10] * p.z + T[14];
-            p = make_float4(x, y, z, p.w);
+            const float3 x3 = transform_point(T, p.x, p.y, p.z);
+            p = make_float4(x3.x, x3.y, x3.z, p.w);
             if (t == 0) X[i] = p;
         }
         const float q[3] = {p.x, p.y, p.z};

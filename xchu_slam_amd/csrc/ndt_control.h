@@ -434,26 +434,8 @@ __device__ __forceinline__ void solve_loop(AlignState* st, const double* spec_dp
 
 __constant__ unsigned c_angle_code[69] = NDT_ANGLE_TABLE_CODE;
 
-// For the tail's fast path: the sin/cos of x_t's angles by ONE wave (lanes 0-2: the f32 AngleAxis sin/cos, lanes 3-5:
-// the f64 angle-derivative sin/cos); pass_tables, after a workgroup barrier: T and the tables from them (also the
-// second half of prepare_pass_parallel)
-__device__ __forceinline__ void pass_sincos_wave(const AlignState* st, double* sc) {
-    const int lane = threadIdx.x & 63;
-    if (lane < 3) {
-        // sin and cos of one angle side by side (sincosf_dr2: the bits of sinf_dr / cosf_dr, two independent chains)
-        float sn, cs;
-        sincosf_dr2((float)st->x_t[3 + lane], &sn, &cs);
-        sc[2 * lane] = (double)sn;
-        sc[2 * lane + 1] = (double)cs;
-    } else if (lane < 6) {
-        const int k = lane - 3;
-        const double a = st->x_t[3 + k];
-        double sn = 0.0, cs = 1.0;
-        if (!(fabs(a) < 10e-5)) sincos(a, &sn, &cs);
-        sc[6 + 2 * k] = sn;
-        sc[6 + 2 * k + 1] = cs;
-    }
-}
+// The second half of prepare_pass_parallel, after its workgroup barrier: T and the angle tables from the sin / cos in
+// s_sc ([0..5] the f32 AngleAxis sin, cos of the three angles, [6..11] the f64 angle-derivative ones)
 template <int NW>
 __device__ void pass_tables(AlignState* st, const double* s_sc) {
     static_assert(NW >= 4, "T is assembled by wave 3");
@@ -738,15 +720,13 @@ __device__ __forceinline__ void after_solve_store(AlignState& st, const StepRegs
     }
 }
 
-// tail_control's fast paths (see there): 1 = the step on one lane, then the sin / cos on one wave; 3 = the step in
-// registers on waves 0 and 1, the f32 and the f64 sin / cos on one wave each
-#ifndef NDT_TAIL_FAST
-#define NDT_TAIL_FAST 3
-#endif
-template <int NW, int FAST = NDT_TAIL_FAST>
+// The control step of a pass's tail on the LDS-staged state, all waves of the workgroup: the speculative LU solve on wave
+// 0 beside the pass record and the state machine on wave 1, then the fast path (below) or solve_loop /
+// prepare_pass_parallel
+template <int NW>
 __device__ __forceinline__ void tail_control(AlignState& s_st, const double* red, PassRecordDev* hist, int hist_cap,
                                              unsigned long long* ts) {
-    static_assert(FAST != 3 || NW >= 3, "fast path 3 runs the step on waves 0 and 1 and a sin / cos on wave 2");
+    static_assert(NW >= 3, "the fast path runs the step on waves 0 and 1 and a sin / cos on wave 2");
     __shared__ double s_spec_dp[6];
     __shared__ int s_spec_fail;
     const bool spec = s_st.phase == 0 || s_st.pass_kind == PASS_FULL;
@@ -764,148 +744,116 @@ __device__ __forceinline__ void tail_control(AlignState& s_st, const double* red
     } else if (wv == 1) {
         control_record_wave(&s_st, red, hist, hist_cap);
         if ((threadIdx.x & 63) == 0) NDT_TAIL_STAMP(4);
-        if (FAST == 3) {
-            control_step_wave(&s_st, red);
-        } else if ((threadIdx.x & 63) == 0) {
-            control_step(&s_st, red);
-        }
+        control_step_wave(&s_st, red);
         if ((threadIdx.x & 63) == 0) NDT_TAIL_STAMP(5);
     }
     bool tables_done = false;
-    if (FAST == 3) {
-        // fast path 3 (the Newton step after a speculatively solved direction, nearly every pass): after the state
-        // machine asked for the solve, waves 0, 1 and 2 each take the step in registers (wave 0 from its LU registers,
-        // the others from the LDS copy: the same bits); wave 0 builds T (the f32 AngleAxis sin / cos on lanes 0-2), wave 1
-        // the angle tables (the f64 sin / cos on lanes 0-2, one entry per lane), wave 2 writes the state one field per
-        // lane, side by side; one barrier ends the tail.  Anything else continues as solve_loop / prepare_pass_parallel.
-        // the angle-table codes of wave 1's entries (t = lane, 64 + lane), loaded now, used after the state machine
-        const int lane = threadIdx.x & 63;
-        const unsigned code0 = (wv == 1) ? c_angle_code[lane] : 0u;
-        const unsigned code1 = (wv == 1 && lane < 5) ? c_angle_code[64 + lane] : 0u;
-        __shared__ int s_go3;
-        __shared__ double s_fv3[8];
-        lds_barrier();
-        if (spec && s_st.want_solve && !s_spec_fail) {  // uniform
-            if (wv <= 2) {
-                StepRegs o;
-                double dpi[6];
+    // Fast path (the Newton step after a speculatively solved direction, nearly every pass): after the state machine
+    // asked for the solve, waves 0, 1 and 2 each take the step in registers (wave 0 from its LU registers, the others
+    // from the LDS copy: the same bits); wave 0 builds T (the f32 AngleAxis sin / cos on lanes 0-2), wave 1 the angle
+    // tables (the f64 sin / cos on lanes 0-2, one entry per lane), wave 2 writes the state one field per lane, side by
+    // side; one barrier ends the tail.  Anything else (a second solve request, a paused chain) continues as solve_loop /
+    // prepare_pass_parallel.
+    // The angle-table codes of wave 1's entries (t = lane, 64 + lane), loaded now, used after the state machine
+    const int lane = threadIdx.x & 63;
+    const unsigned code0 = (wv == 1) ? c_angle_code[lane] : 0u;
+    const unsigned code1 = (wv == 1 && lane < 5) ? c_angle_code[64 + lane] : 0u;
+    __shared__ int s_go3;
+    __shared__ double s_fv3[8];
+    lds_barrier();
+    if (spec && s_st.want_solve && !s_spec_fail) {  // uniform
+        if (wv <= 2) {
+            StepRegs o;
+            double dpi[6];
 #pragma unroll
-                for (int k = 0; k < 6; ++k) dpi[k] = wv == 0 ? x_lu[k] : s_spec_dp[k];
-                const bool ok = after_solve_regs(s_st, dpi, o);
-                double xa = 0.0;
+            for (int k = 0; k < 6; ++k) dpi[k] = wv == 0 ? x_lu[k] : s_spec_dp[k];
+            const bool ok = after_solve_regs(s_st, dpi, o);
+            double xa = 0.0;
 #pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    if (lane == k) xa = o.xt[3 + k];
-                if (wv == 0) {
-                    // convertTransform(x_t): the f32 AngleAxis sin / cos on lanes 0-2, broadcast, T on lane 0 (the
-                    // operations of pass_tables' T), the constant table columns; then the state writes
-                    float sn = 0.f, cs = 1.f;
-                    if (ok && lane < 3) sincosf_dr2((float)xa, &sn, &cs);
-                    float sa[3], ca[3];
+            for (int k = 0; k < 3; ++k)
+                if (lane == k) xa = o.xt[3 + k];
+            if (wv == 0) {
+                // convertTransform(x_t): the f32 AngleAxis sin / cos on lanes 0-2, broadcast, T on lane 0 (the
+                // operations of pass_tables' T), the constant table columns; then the state writes
+                float sn = 0.f, cs = 1.f;
+                if (ok && lane < 3) sincosf_dr2((float)xa, &sn, &cs);
+                float sa[3], ca[3];
 #pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        sa[a] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sn), a));
-                        ca[a] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cs), a));
+                for (int a = 0; a < 3; ++a) {
+                    sa[a] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sn), a));
+                    ca[a] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cs), a));
+                }
+                if (ok) {
+                    if (lane == 0) {
+                        float R3[3][9];
+                        for (int a = 0; a < 3; ++a) angle_axis_sc(sa[a], ca[a], a, R3[a]);
+                        float Rxy[9], R[9];
+                        mat3_mul_f(R3[0], R3[1], Rxy);
+                        mat3_mul_f(Rxy, R3[2], R);
+                        for (int j = 0; j < 3; ++j)
+                            for (int i = 0; i < 3; ++i) s_st.T[i + 4 * j] = R[i + 3 * j];
+                        s_st.T[3] = 0.f; s_st.T[7] = 0.f; s_st.T[11] = 0.f;
+                        s_st.T[12] = (float)o.xt[0]; s_st.T[13] = (float)o.xt[1]; s_st.T[14] = (float)o.xt[2]; s_st.T[15] = 1.f;
+                    } else if (lane >= 32 && lane < 40) {
+                        s_st.jang[lane - 32][3] = 0.f;
+                    } else if (lane >= 40 && lane < 56) {
+                        s_st.hang[lane - 40][3] = 0.f;
+                    } else if (lane >= 56 && lane < 59) {
+                        s_st.hang[15][lane - 56] = 0.f;
                     }
-                    if (ok) {
-                        if (lane == 0) {
-                            float R3[3][9];
-                            for (int a = 0; a < 3; ++a) angle_axis_sc(sa[a], ca[a], a, R3[a]);
-                            float Rxy[9], R[9];
-                            mat3_mul_f(R3[0], R3[1], Rxy);
-                            mat3_mul_f(Rxy, R3[2], R);
-                            for (int j = 0; j < 3; ++j)
-                                for (int i = 0; i < 3; ++i) s_st.T[i + 4 * j] = R[i + 3 * j];
-                            s_st.T[3] = 0.f; s_st.T[7] = 0.f; s_st.T[11] = 0.f;
-                            s_st.T[12] = (float)o.xt[0]; s_st.T[13] = (float)o.xt[1]; s_st.T[14] = (float)o.xt[2]; s_st.T[15] = 1.f;
-                        } else if (lane >= 32 && lane < 40) {
-                            s_st.jang[lane - 32][3] = 0.f;
-                        } else if (lane >= 40 && lane < 56) {
-                            s_st.hang[lane - 40][3] = 0.f;
-                        } else if (lane >= 56 && lane < 59) {
-                            s_st.hang[15][lane - 56] = 0.f;
-                        }
-                    }
-                    if (threadIdx.x == 0) s_go3 = ok ? 1 : 0;
-                } else if (wv == 2) {
-                    // the state writes, one field per lane, beside waves 0 and 1 (p, g, score and the step bounds it
-                    // read are written by no one here)
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-                    if (ok) after_solve_store(s_st, o, 0);
-                } else {
-                    // computeAngleDerivatives(x_t): the f64 sin / cos on lanes 0-2, the eight factors {1, sx, cx, sy,
-                    // cy, sz, cz, 0} through LDS, entry t = lane (and 64 + lane) on every lane: angle_table_entry's
-                    // operations with its factor lookups as indexed LDS reads
-                    double sn = 0.0, cs = 1.0;
-                    if (ok && lane < 3 && !(fabs(xa) < 10e-5)) sincos(xa, &sn, &cs);
-                    if (lane < 3) {
-                        s_fv3[1 + 2 * lane] = sn;
-                        s_fv3[2 + 2 * lane] = cs;
-                    } else if (lane == 3) {
-                        s_fv3[0] = 1.0;
-                        s_fv3[7] = 0.0;
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-                    if (ok) {
+                }
+                if (threadIdx.x == 0) s_go3 = ok ? 1 : 0;
+            } else if (wv == 2) {
+                // the state writes, one field per lane, beside waves 0 and 1 (p, g, score and the step bounds it
+                // read are written by no one here)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+                if (ok) after_solve_store(s_st, o, 0);
+            } else {
+                // computeAngleDerivatives(x_t): the f64 sin / cos on lanes 0-2, the eight factors {1, sx, cx, sy,
+                // cy, sz, cz, 0} through LDS, entry t = lane (and 64 + lane) on every lane: angle_table_entry's
+                // operations with its factor lookups as indexed LDS reads
+                double sn = 0.0, cs = 1.0;
+                if (ok && lane < 3 && !(fabs(xa) < 10e-5)) sincos(xa, &sn, &cs);
+                if (lane < 3) {
+                    s_fv3[1 + 2 * lane] = sn;
+                    s_fv3[2 + 2 * lane] = cs;
+                } else if (lane == 3) {
+                    s_fv3[0] = 1.0;
+                    s_fv3[7] = 0.0;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+                if (ok) {
 #pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            const int t = h * 64 + lane;
-                            if (t < 69) {
-                                const unsigned code = h ? code1 : code0;
-                                double a = s_fv3[code & 7];
-                                if (code & (1u << 9)) a = -a;
-                                double v = (a * s_fv3[(code >> 3) & 7]) * s_fv3[(code >> 6) & 7];
-                                if (code & (1u << 20)) {
-                                    double d = s_fv3[(code >> 10) & 7];
-                                    if (code & (1u << 19)) d = -d;
-                                    v = v + (d * s_fv3[(code >> 13) & 7]) * s_fv3[(code >> 16) & 7];
-                                }
-                                const int r = t / 3, c = t - 3 * r;
-                                if (r < 8) { s_st.jang[r][c] = (float)v; s_st.jang_d[r][c] = v; }
-                                else { s_st.hang[r - 8][c] = (float)v; s_st.hang_d[r - 8][c] = v; }
+                    for (int h = 0; h < 2; ++h) {
+                        const int t = h * 64 + lane;
+                        if (t < 69) {
+                            const unsigned code = h ? code1 : code0;
+                            double a = s_fv3[code & 7];
+                            if (code & (1u << 9)) a = -a;
+                            double v = (a * s_fv3[(code >> 3) & 7]) * s_fv3[(code >> 6) & 7];
+                            if (code & (1u << 20)) {
+                                double d = s_fv3[(code >> 10) & 7];
+                                if (code & (1u << 19)) d = -d;
+                                v = v + (d * s_fv3[(code >> 13) & 7]) * s_fv3[(code >> 16) & 7];
                             }
+                            const int r = t / 3, c = t - 3 * r;
+                            if (r < 8) { s_st.jang[r][c] = (float)v; s_st.jang_d[r][c] = v; }
+                            else { s_st.hang[r - 8][c] = (float)v; s_st.hang_d[r - 8][c] = v; }
                         }
                     }
                 }
             }
-            lds_barrier();
-            if (s_go3) {
-                if (ts && threadIdx.x == 0) ts[7] = __builtin_amdgcn_s_memrealtime();
-                if (threadIdx.x == 0) { NDT_TAIL_STAMP(0); NDT_TAIL_STAMP(1); NDT_TAIL_STAMP(2); NDT_TAIL_STAMP(3); }
-                tables_done = true;
-            }
-        }
-    }
-    if (FAST == 1) {
-    // fast path (the Newton step after a speculatively solved direction, nearly every pass): wave 0 takes the step
-    // (lane 0) and, without a workgroup barrier, the sin/cos of the new angles (lanes 0-5); one barrier, then T and the
-    // tables.  Any other case (a second solve request, a paused chain) continues as solve_loop / prepare_pass_parallel.
-    __shared__ double s_sc[12];
-    lds_barrier();
-    if (spec && s_st.want_solve) {
-        if (wv == 0) {
-            if (threadIdx.x == 0) {
-                NDT_TAIL_STAMP(0);
-                NDT_TAIL_STAMP(1);
-                newton_after_solve(&s_st, s_spec_dp, s_spec_fail);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-            if (!s_st.want_solve && s_st.needs_tables) pass_sincos_wave(&s_st, s_sc);
         }
         lds_barrier();
-        if (!s_st.want_solve) {
+        if (s_go3) {
             if (ts && threadIdx.x == 0) ts[7] = __builtin_amdgcn_s_memrealtime();
-            if (threadIdx.x == 0) NDT_TAIL_STAMP(2);
-            if (s_st.needs_tables) pass_tables<NW>(&s_st, s_sc);
+            if (threadIdx.x == 0) { NDT_TAIL_STAMP(0); NDT_TAIL_STAMP(1); NDT_TAIL_STAMP(2); NDT_TAIL_STAMP(3); }
             tables_done = true;
         }
-    }
     }
     if (!tables_done) {
         solve_loop(&s_st, spec ? s_spec_dp : nullptr, &s_spec_fail);

@@ -30,6 +30,13 @@ __device__ __forceinline__ int voxel_lookup(bool dense, const int* __restrict__ 
     return dense ? grid[key] : hash_find(table, log2cap, key);
 }
 
+// pcl::transformPointCloud of one point, f32: ((m0*x + m1*y) + m2*z) + m3 per row of the column-major T
+// (Eigen::Matrix4f); -ffp-contract=off, so no product is fused into an add
+__device__ __forceinline__ float3 transform_point(const float* __restrict__ T, float x, float y, float z) {
+    return make_float3(T[0] * x + T[4] * y + T[8] * z + T[12], T[1] * x + T[5] * y + T[9] * z + T[13],
+                       T[2] * x + T[6] * y + T[10] * z + T[14]);
+}
+
 // Block-wide exclusive scan of one int per thread (kBlock threads); *total = sum.  Two barriers.
 // Workgroup barrier that orders LDS only: it does not wait for this wave's outstanding global loads/stores
 // (HIP's __syncthreads() is a fence on every address space, i.e. also an s_waitcnt vmcnt(0)).
@@ -192,7 +199,7 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[NV], double* re
     }
 }
 
-// Split accumulation (NDT_SPLIT_ACC, derivatives.hip): lanes 0-31 of a wave hold the sums of the 22 "low" terms of every
+// Split accumulation (the direct passes, derivatives.hip): lanes 0-31 of a wave hold the sums of the 22 "low" terms of every
 // pair (score, g0..g2, H columns 0..2), lanes 32-63 the 22 "high" ones (g3..g5, the pair count, H columns 3..5): each pair's
 // terms are exchanged across the half-waves (v_permlane32_swap) as they are produced, so that a lane keeps 22 f64 sums
 // instead of 44.  Value k of the low / high set -> index of the 44 reduced values:

@@ -44,8 +44,8 @@ struct PassGeom {
 };
 
 // Workgroups of at most one per CU (of this ctx's share) x the pass's workgroups per CU, and at least ~64 points each
-inline int direct_blocks(const PassShape& s, bool lead, int n, int ppt, bool one_tile = false) {
-    return std::max(1, std::min(s.n_cu * pass_wgs_per_cu(s.search, lead, ppt, one_tile), ceil_div(n, 64)));
+inline int direct_blocks(const PassShape& s, bool lead, int n, int ppt) {
+    return std::max(1, std::min(s.n_cu * pass_wgs_per_cu(s.search, lead, ppt), ceil_div(n, 64)));
 }
 
 // Last-workgroup-tail passes of large clouds as a grid of one-tile workgroups (k_pass_direct<S, 1, true>: no tile loop,
@@ -69,18 +69,10 @@ inline bool pass_ppt2(const PassShape& s) {
     return max_cloud < (1ll << 22) && rounds1 >= 4;
 }
 
-// Last-workgroup-tail passes of one point per thread whose point bucket fits one tile per workgroup at three workgroups
-// per CU (C4's 120 k-point pairs): k_pass_direct<S, 1, true>, three waves per SIMD
-inline bool direct_one_tile(const PassShape& s) {
-    if (!NDT_DIRECT_ONE_TILE || s.search == S_DIRECT26 || pass_ppt2(s)) return false;
-    const int n = geom_points(std::max(1, s.N));
-    return (long long)n <= (long long)direct_blocks(s, false, n, 1, true) * pass_block(s.search, false);
-}
-
 // leading-tail passes in one tile per workgroup (k_pass_lead<S, true>): DIRECT7 / DIRECT1 whose point bucket fits one
 // 768-point tile per CU
 inline bool lead_one_tile(const PassShape& s) {
-    return NDT_LEAD_ONE_TILE && s.search != S_DIRECT26 && (long long)geom_points(std::max(1, s.N)) <= (long long)s.n_cu * kLeadBlock1;
+    return s.search != S_DIRECT26 && (long long)geom_points(std::max(1, s.N)) <= (long long)s.n_cu * kLeadBlock1;
 }
 
 inline PassGeom direct_geom(const PassShape& s, bool lead) {
@@ -93,7 +85,7 @@ inline PassGeom direct_geom(const PassShape& s, bool lead) {
         return g;
     }
     const int ppt = (!lead && pass_ppt2(s)) ? 2 : 1;
-    g.nb = direct_blocks(s, lead, n, ppt, !lead && direct_one_tile(s));
+    g.nb = direct_blocks(s, lead, n, ppt);
     const int per_tile = g.block * ppt;
     const int rounds = ceil_div(n, g.nb * per_tile);
     g.ppb = ceil_div(n, g.nb * rounds);
@@ -119,7 +111,7 @@ inline bool describe_pass(const PassShape& s, int which, int out[8]) {
         out[1] = g.block;
         out[2] = g.ppb;
         out[3] = (!lead && pass_ppt2(s)) ? 2 : 1;
-        out[4] = lead ? (lead_one_tile(s) ? 1 : 0) : ((direct_one_tile(s) || grid_one_tile(s)) ? 1 : 0);
+        out[4] = (lead ? lead_one_tile(s) : grid_one_tile(s)) ? 1 : 0;
     }
     out[5] = ceil_div(n, (long long)out[0] * out[2]);
     const bool two = which != 1 && out[0] > kTwoLevelMinBlocks;

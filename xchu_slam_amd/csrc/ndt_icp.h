@@ -9,7 +9,7 @@
 namespace ndt {
 
 constexpr int kIcpBlock = 256;                     // threads per k_icp_pass workgroup
-constexpr int kIcpTeam = NDT_FIT_TEAM;             // lanes per query (the k_fitness team)
+constexpr int kIcpTeam = kFitTeam;             // lanes per query (the k_fitness team)
 constexpr int kIcpTeams = kIcpBlock / kIcpTeam;    // queries per workgroup step
 constexpr int kIcpMaxBlocks = 1024;                // grid cap: the tail reads 17 partials per workgroup
 constexpr int kIcpSums = 17;                       // sum d2, sum p[3], sum q[3], sum p q^T [9], n

@@ -23,7 +23,7 @@
 
 namespace ndt {
 
-constexpr int kNnTeam = NDT_FIT_TEAM;  // lanes per query (ndt_types.h)
+constexpr int kNnTeam = kFitTeam;  // lanes per query (ndt_types.h)
 constexpr int kNnU = 8;                // point loads in flight per lane (clamped repeats past a range's end)
 constexpr int kNnCells = 2;            // ring-cube cells per lane per step: their table, offset and point loads issued together
 

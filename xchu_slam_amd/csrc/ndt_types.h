@@ -26,48 +26,20 @@ constexpr int kLeadBlock = 512;
 // one-tile leading-tail passes (every workgroup's points fit one tile): 768 threads, 12 waves per CU = three per SIMD; with
 // split sums and no tile loop the kernel fits 168 VGPRs
 constexpr int kLeadBlock1 = 768;
-// 1: split sums in the pass kernels (derivatives.hip SplitSink: 22 f64 sums per lane instead of 44)
-#ifndef NDT_SPLIT_ACC
-#define NDT_SPLIT_ACC 1
-#endif
-// the one-tile kernel's three-wave register budget needs the split sums
-#ifndef NDT_LEAD_ONE_TILE
-#define NDT_LEAD_ONE_TILE NDT_SPLIT_ACC
-#endif
-// 1: last-workgroup-tail passes whose geometry has one tile per workgroup run the one-tile kernel (three waves per SIMD)
-#ifndef NDT_DIRECT_ONE_TILE
-#define NDT_DIRECT_ONE_TILE 0
-#endif
 constexpr int kDirectBlock = 256;
-// 1: the direct passes' pair arithmetic issued as packed f32 pairs (pair_pk, ndt_pair.h; bitwise the same results)
-#ifndef NDT_PACKED_PAIR
-#define NDT_PACKED_PAIR 1
-#endif
-// 1: DIRECT7 passes over a dense grid load the centre row's three cells (0, +x, -x) with one dwordx3 load
-#ifndef NDT_ROW_TRIPLE
-#define NDT_ROW_TRIPLE 1
-#endif
-// 1: DIRECT7 passes keep each source point's cell and probe results across the passes of an align (neighbour cache)
-#ifndef NDT_NBR_CACHE
-#define NDT_NBR_CACHE 1
-#endif
 __host__ __device__ constexpr int pass_block(int search, bool lead, bool one_tile = false) {
     return search == 1 /*DIRECT26*/ ? kBlock : (lead ? (one_tile ? kLeadBlock1 : kLeadBlock) : kDirectBlock);
 }
-// waves per SIMD the register allocation of one-point-per-thread k_pass_direct (DIRECT7 / DIRECT1) is held to: 2, or 3
-// with split accumulation (its tile state spills around the pair loop, the pair loop itself stays in registers); the
-// two-points-per-thread tiles hold 77 KB of LDS, two workgroups per CU, and stay at 2
-#ifndef NDT_PASS_WAVES
-#define NDT_PASS_WAVES 2
-#endif
-// one_tile: a one-point-per-thread geometry with one tile per workgroup (no tile loop: the split sums are not live across
-// the probes) runs three waves per SIMD
+// waves per SIMD the register allocation of k_pass_direct (DIRECT7 / DIRECT1) is held to: 2 (at 3 the tile state of the
+// one-point-per-thread tile loop spills around the pair loop; the two-points-per-thread tiles hold 77 KB of LDS, two
+// workgroups per CU).  one_tile: a one-point-per-thread geometry with one tile per workgroup (no tile loop: the split
+// sums are not live across the probes) runs three waves per SIMD
 __host__ __device__ constexpr int pass_waves(int search, int ppt, bool one_tile = false) {
-    return search == 1 ? 1 : (ppt == 2 ? 2 : (one_tile ? 3 : NDT_PASS_WAVES));
+    return search == 1 ? 1 : ((ppt != 2 && one_tile) ? 3 : 2);
 }
-// k_pass_direct workgroups (4 waves) per CU: one per wave slot of a SIMD
-__host__ __device__ constexpr int pass_wgs_per_cu(int search, bool lead, int ppt, bool one_tile = false) {
-    return (search == 1 || lead) ? 1 : pass_waves(search, ppt, one_tile);
+// k_pass_direct workgroups (4 waves) per CU of the tile-loop geometries: one per wave slot of a SIMD
+__host__ __device__ constexpr int pass_wgs_per_cu(int search, bool lead, int ppt) {
+    return (search == 1 || lead) ? 1 : pass_waves(search, ppt);
 }
 constexpr int kNumAcc = 44;          // score + g[6] + H[36] + pairs
 constexpr int kEmptyKey = -1;        // empty hash slot
@@ -142,14 +114,10 @@ constexpr int kBuildErrMerge = 4;     // a merge-extended build beyond the exact
 constexpr int kMergeTileKeys = 2048;                   // outputs per workgroup of k_merge_append
 constexpr int kFitBlockCells = 512;                    // 8 x 8 x 8 cells per block
 // threads per k_fitness workgroup (a workgroup ends with its slowest query: one wave keeps a far query from holding three)
-#ifndef NDT_FIT_BLOCK
-#define NDT_FIT_BLOCK 64
-#endif
+constexpr int kFitBlock = 64;
 // lanes per getFitnessScore query (k_fitness team)
-#ifndef NDT_FIT_TEAM
-#define NDT_FIT_TEAM 16
-#endif
-static_assert(NDT_FIT_BLOCK >= 64, "k_fitness: a group's partials are reduced one per thread");
+constexpr int kFitTeam = 16;
+static_assert(kFitBlock >= 64, "k_fitness: a group's partials are reduced one per thread");
 constexpr int kFitGroup = 64;                          // k_fitness workgroups per first-level ticket
 constexpr int kFitTicketStride = 64;                   // words between ticket counters (own cache lines / channels)
 constexpr long long kFitMaxKeys = 1LL << 25;           // key range cap of layout 1 (cells doubled until it fits)

@@ -16,12 +16,8 @@ __global__ __launch_bounds__(kBlock) void k_transform(const float4* __restrict__
     if (i >= n) return;
     const float* T = st->T;
     const float4 p = src[i];
-    float4 o;
-    o.x = T[0] * p.x + T[4] * p.y + T[8] * p.z + T[12];
-    o.y = T[1] * p.x + T[5] * p.y + T[9] * p.z + T[13];
-    o.z = T[2] * p.x + T[6] * p.y + T[10] * p.z + T[14];
-    o.w = 1.0f;
-    out[i] = o;
+    const float3 o = transform_point(T, p.x, p.y, p.z);
+    out[i] = make_float4(o.x, o.y, o.z, 1.0f);
 }
 
 // pcl::transformPointCloud(in, out, T) for a caller-given f32 transform (odom_node.cpp:220, 290): x,y,z

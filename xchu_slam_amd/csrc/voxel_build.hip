@@ -305,10 +305,7 @@ constexpr int kSpinLimit = 1 << 15;
 // Sorts of at most kTwoLevelTiles tiles (every sort whose tiles can all be resident) resolve the look-back in two levels
 // over groups of kGroupTiles tiles; the group totals sit behind the tiles' words: [4 passes][groups][256] (host_sort.hip
 // radix_status_words)
-#ifndef NDT_TWOLEVEL_TILES
-#define NDT_TWOLEVEL_TILES 1024
-#endif
-constexpr int kTwoLevelTiles = NDT_TWOLEVEL_TILES, kGroupTiles = 16;
+constexpr int kTwoLevelTiles = 1024, kGroupTiles = 16;
 
 // Profiling build only (-DNDT_SORT_STAMPS, `make VARIANT=sortdbg VFLAGS=-DNDT_SORT_STAMPS`): phase stamps (100 MHz device
 // clock) of the first, the middle and the last tile of each pass, per instantiation, summed over the launches;
@@ -534,10 +531,7 @@ __global__ __launch_bounds__(kBlock) void k_radix_onesweep(int* __restrict__ k0,
         // walk back over earlier tiles kLookBack at a time (their status loads in flight together), summing
         // aggregates until the first inclusive prefix; a window stops at the first tile not yet published and is
         // re-read from there
-#ifndef NDT_LOOKBACK
-#define NDT_LOOKBACK 8
-#endif
-        constexpr int kLookBack = NDT_LOOKBACK;
+        constexpr int kLookBack = 8;
         int t = tile - 1;
         int spin = 0;
         for (;;) {
@@ -1139,8 +1133,8 @@ __global__ __launch_bounds__(kBlock) void k_src_keys(const float4* __restrict__ 
     __syncthreads();
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         const float4 p = src[i];
-        const float x[3] = {T[0] * p.x + T[4] * p.y + T[8] * p.z + T[12], T[1] * p.x + T[5] * p.y + T[9] * p.z + T[13],
-                            T[2] * p.x + T[6] * p.y + T[10] * p.z + T[14]};
+        const float3 x3 = transform_point(T, p.x, p.y, p.z);
+        const float x[3] = {x3.x, x3.y, x3.z};
         int key = 0;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
