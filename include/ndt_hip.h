@@ -25,7 +25,8 @@ extern "C" {
  * 2 = ndt_result.solver_fallbacks appended, ndt_pass_phases 20 -> 22 doubles; 3 = the Scan Context surface (ndt_sc_params,
  * ndt_sc_result; no earlier layout changed); 4 = the pose-graph surface (ndt_pgo_params, ndt_pgo_result, ndt_pgo_record;
  * no earlier layout changed); 5 = the ISC surface (ndt_isc_params, ndt_isc_result); no earlier layout changed; 6 =
- * ndt_pass_geometry (its 8 ints); no earlier layout changed.  A caller built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
+ * ndt_pass_geometry (its 8 ints); no earlier layout changed; ground surface added at 6, size-checked (ndt_ground_params and
+ * ndt_ground_result start with their own size, which the library checks; no earlier layout changed).  A caller built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
 #define NDT_HIP_ABI_VERSION 6
 
 typedef struct ndt_ctx ndt_ctx;
@@ -623,6 +624,85 @@ ndt_status ndt_filter_scan_device(ndt_ctx* ctx, const ndt_filter_params* prm, co
 /* per-point SOR distances and threshold of the last filter_scan (test hook): dist[0..n_voxel) in voxel order,
  * thr = {threshold, mean, stddev}; *n_voxel = points after the voxel filter. */
 ndt_status ndt_filter_last_stats(ndt_ctx* ctx, float* dist, size_t cap, size_t* n_voxel, double thr[3]);
+
+/* filter_node's ground detection (xchu_mapping/src/filter_node.cpp:53-216: DetectPlane with PlaneClip and
+ * NormalFiltering; defaults filter_node.h:62-71): the floor coefficients of /ground_coeffs and the /normal_ground_points,
+ * /ground_points and /no_ground_points clouds.  tilt -> height clip (two PlaneClipper3D calls) -> normal filter (k nearest
+ * neighbours within the clipped cloud, normal flipped to the viewpoint (0,0,sensor_height), |n.z| against
+ * normal_filter_thresh) -> tilt back -> pcl::RandomSampleConsensus over SampleConsensusModelPlane (the model's
+ * boost::mt19937 seeded 12345 per scan) -> the gates on the inlier count and on the floor's normal.  PCL is not part of
+ * the reference tree: the semantics are the restatement of DESIGN.md §2 "Ground" (parity with PCL unpinned).
+ * Both structs start with their own size: the caller sets struct_size = sizeof(its struct) before any call that takes
+ * one, and the library answers NDT_EINVAL when that is not the size it was built with. */
+typedef enum {
+    NDT_GROUND_OK = 0,
+    NDT_GROUND_TOO_FEW_POINTS = 1,   /* fewer than floor_pts_thresh points after the normal filter (:144)  */
+    NDT_GROUND_TOO_FEW_INLIERS = 2,  /* fewer than floor_pts_thresh inliers, or no model at all (:158)       */
+    NDT_GROUND_NOT_VERTICAL = 3      /* the floor's normal is further than floor_normal_thresh from vertical (:169) */
+} ndt_ground_reason;
+typedef enum { NDT_GROUND_CLOUD_NORMAL = 0, NDT_GROUND_CLOUD_GROUND = 1, NDT_GROUND_CLOUD_NO_GROUND = 2 } ndt_ground_cloud_kind;
+
+typedef struct {
+    uint32_t struct_size;        /* sizeof(ndt_ground_params), set by the caller                                  */
+    double tilt_deg;             /* filter_node.h:63   default 0                                                    */
+    double sensor_height;        /* :64                default 2.0                                                  */
+    double height_clip_range;    /* :65                default 2.5 (keeps -4.5 <= z < 0.5 with the defaults)        */
+    int floor_pts_thresh;        /* :67                default 512 (>= 3)                                           */
+    double floor_normal_thresh;  /* :68  degrees       default 10                                                   */
+    int use_normal_filtering;    /* :69                default 1                                                    */
+    double normal_filter_thresh; /* :70  degrees       default 20                                                   */
+    int normal_k;                /* NormalEstimation::setKSearch (filter_node.cpp:81)  default 10 (1..20)           */
+    double ransac_threshold;     /* setDistanceThreshold (:151)                        default 0.1                  */
+    double ransac_probability;   /* pcl::SampleConsensus probability_                  default 0.99                 */
+    int ransac_max_iterations;   /* pcl::SampleConsensus max_iterations_               default 1000 (1..4000)       */
+    int literal_no_ground;       /* 0 (default): /no_ground_points is the input without the points the inliers came
+                                    from; 1: the reference's form (:197-202), which removes the input points whose
+                                    index equals an inlier's index in the filtered cloud                            */
+    float cloud_leaf;            /* downSizeNoGroundFrames leaf (:36) applied by ndt_ground_cloud, default 0.2; 0 = raw */
+} ndt_ground_params;
+
+typedef struct {
+    uint32_t struct_size;        /* sizeof(ndt_ground_result), set by the caller                                  */
+    int found;                   /* 0: the reference returns Vector4f::Identity() (see reason)                     */
+    float coeffs[4];             /* a, b, c, d of the floor (normal upward); zeros when not found                   */
+    int n_input, n_clipped, n_normal, n_inliers;  /* points: in, after the clip, after the normal filter, inliers   */
+    int iterations, skipped;     /* RandomSampleConsensus iterations_ and its skipped (degenerate) samples          */
+    int winner[3];               /* the winning sample as indices into the input cloud (-1 without a model)         */
+    int reason;                  /* ndt_ground_reason                                                               */
+    int stream_fallbacks;        /* times the scan's sampler ran past the uploaded generator table and the host
+                                    continued the stream                                                            */
+    double k;                    /* the loop's last bound on the iterations                                         */
+} ndt_ground_result;
+
+ndt_status ndt_ground_default_params(ndt_ground_params* out);
+/* host cloud (as ndt_filter_scan's) -> the floor; synchronises.  The clouds stay on the device until the next detect. */
+ndt_status ndt_ground_detect(ndt_ctx* ctx, const ndt_ground_params* prm, const float* xyzi, size_t n, size_t stride_bytes,
+                             int intensity_offset, ndt_ground_result* result);
+/* device float4 (x,y,z,i) cloud; it is copied, so the caller may reuse the buffer after the call. */
+ndt_status ndt_ground_detect_device(ndt_ctx* ctx, const ndt_ground_params* prm, const float* d_in4, size_t n, ndt_ground_result* result);
+/* One cloud of the last detect (ndt_ground_cloud_kind), passed through pcl::VoxelGrid(cloud_leaf) unless the leaf is 0:
+ * up to cap points (x,y,z,i) to out4, *n_out = the cloud's size.  The ground and no-ground clouds are empty when no floor
+ * was found (the reference publishes neither then). */
+ndt_status ndt_ground_cloud(ndt_ctx* ctx, int which, float* out4, size_t cap, size_t* n_out);
+/* the same into device memory (d_out4: capacity n_input points) */
+ndt_status ndt_ground_cloud_device(ndt_ctx* ctx, int which, float* d_out4, size_t cap, size_t* n_out);
+/* CloudFilter::Run (filter_node.cpp:218-273 + DetectPlane): ndt_filter_scan_device, then the detect over its output
+ * without a host copy of the cloud in between.  d_out4 / *n_out: the filtered scan, as ndt_filter_scan_device's. */
+ndt_status ndt_filter_ground_scan(ndt_ctx* ctx, const ndt_filter_params* fprm, const ndt_ground_params* gprm, const float* d_in4,
+                                  size_t n, float* d_out4, size_t* n_out, ndt_ground_result* result);
+/* hypotheses scored per launch of the plane scoring kernel (the B of DESIGN.md §2 "Ground") */
+int ndt_ground_batch(void);
+/* Test hooks.  Per point of the clipped cloud of the last detect: normal4 = the oriented normal and |n.z| of the
+ * normalised normal (zeros without normal filtering), keep = the filter's flag, origin = its index in the input cloud,
+ * nbr = its normal_k neighbours (indices into the clipped cloud, ascending (d2, index), -1 past the cloud's size);
+ * any pointer may be NULL; *n_out = the clipped cloud's size. */
+ndt_status ndt_ground_last_normals(ndt_ctx* ctx, float* normal4, int* keep, int* origin, int* nbr, size_t cap, size_t* n_out);
+/* Every hypothesis the last detect's loop looked at, in order: its sample (indices into the cloud after the normal
+ * filter), its coefficients before the sign is settled, its inlier count and its status (1 scored, 0 degenerate sample). */
+ndt_status ndt_ground_last_hypotheses(ndt_ctx* ctx, int* triples, float* coeffs, int* counts, int* status, size_t cap, size_t* n_out);
+/* The next detects take these n_triples samples in place of the sampler's (the loop ends where the list does);
+ * n_triples = 0 restores the sampler.  Indices outside the cloud after the normal filter end the list early. */
+ndt_status ndt_ground_set_samples(ndt_ctx* ctx, const int* triples, size_t n_triples);
 
 /* Device-resident variants used by the odom_node replay driver (include/ndt_odom.h), all ordered on the ctx's
  * stream.  d_in4/d_out4 are float4 x,y,z,intensity arrays.

@@ -84,6 +84,48 @@ class FilterParams(C.Structure):
     ]
 
 
+class GroundParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("tilt_deg", C.c_double),
+        ("sensor_height", C.c_double),
+        ("height_clip_range", C.c_double),
+        ("floor_pts_thresh", C.c_int),
+        ("floor_normal_thresh", C.c_double),
+        ("use_normal_filtering", C.c_int),
+        ("normal_filter_thresh", C.c_double),
+        ("normal_k", C.c_int),
+        ("ransac_threshold", C.c_double),
+        ("ransac_probability", C.c_double),
+        ("ransac_max_iterations", C.c_int),
+        ("literal_no_ground", C.c_int),
+        ("cloud_leaf", C.c_float),
+    ]
+
+
+class GroundResult(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("found", C.c_int),
+        ("coeffs", C.c_float * 4),
+        ("n_input", C.c_int),
+        ("n_clipped", C.c_int),
+        ("n_normal", C.c_int),
+        ("n_inliers", C.c_int),
+        ("iterations", C.c_int),
+        ("skipped", C.c_int),
+        ("winner", C.c_int * 3),
+        ("reason", C.c_int),
+        ("stream_fallbacks", C.c_int),
+        ("k", C.c_double),
+    ]
+
+
+# ndt_ground_reason, ndt_ground_cloud_kind
+GROUND_OK, GROUND_TOO_FEW_POINTS, GROUND_TOO_FEW_INLIERS, GROUND_NOT_VERTICAL = range(4)
+GROUND_CLOUD_NORMAL, GROUND_CLOUD_GROUND, GROUND_CLOUD_NO_GROUND = range(3)
+
+
 class IcpParams(C.Structure):
     _fields_ = [
         ("max_corr_dist", C.c_double),
@@ -395,6 +437,19 @@ SIGNATURES = {
                                   C.POINTER(C.c_size_t)]),
     "ndt_filter_scan_device": (C.c_int, [_P, C.POINTER(FilterParams), _P, C.c_size_t, _P, C.POINTER(C.c_size_t)]),
     "ndt_filter_last_stats": (C.c_int, [_P, _FP, C.c_size_t, C.POINTER(C.c_size_t), _DP]),
+    "ndt_ground_default_params": (C.c_int, [C.POINTER(GroundParams)]),
+    "ndt_ground_detect": (C.c_int, [_P, C.POINTER(GroundParams), _FP, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(GroundResult)]),
+    "ndt_ground_detect_device": (C.c_int, [_P, C.POINTER(GroundParams), _P, C.c_size_t, C.POINTER(GroundResult)]),
+    "ndt_ground_cloud": (C.c_int, [_P, C.c_int, _FP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ndt_ground_cloud_device": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ndt_filter_ground_scan": (C.c_int, [_P, C.POINTER(FilterParams), C.POINTER(GroundParams), _P, C.c_size_t, _P,
+                                         C.POINTER(C.c_size_t), C.POINTER(GroundResult)]),
+    "ndt_ground_batch": (C.c_int, []),
+    "ndt_ground_last_normals": (C.c_int, [_P, _FP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_size_t,
+                                          C.POINTER(C.c_size_t)]),
+    "ndt_ground_last_hypotheses": (C.c_int, [_P, C.POINTER(C.c_int), _FP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_size_t,
+                                             C.POINTER(C.c_size_t)]),
+    "ndt_ground_set_samples": (C.c_int, [_P, C.POINTER(C.c_int), C.c_size_t]),
     "ndt_memcpy_d2d": (C.c_int, [_P, _P, _P, C.c_size_t]),
     "ndt_device_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "ndt_device_free": (C.c_int, [_P, _P]),

@@ -272,6 +272,34 @@ struct GicpRun {
     std::vector<GicpRecordDev> hist;
 };
 
+// host_ground.hip — filter_node's ground detection (ndt_ground_detect): the scan's copy and its tilted form, the clipped
+// cloud and the cloud after the normal filter with their input indices, the clipped cloud's neighbour index, the
+// per-point normals, the RANSAC state with its pinned copy (made together), the generator table and the sampler's
+// hash, the hypotheses, the flag arrays of the three clouds, and the last call's record.
+struct GroundRun {
+    DevBuf<GridHeader> d_hdr;           // the compaction scans: pad[0] look-back timeout flag, pad[1] the clipped count
+    NNIndex ix;                         // over the clipped cloud (k_ground_normals)
+    DevBuf<float4> in, tilted, clip, nrm_t, nrm, normal4, cloud, cloud_ds;
+    DevBuf<int> flags, idx, clip_org, nrm_org, nbr, gflag, mark;
+    DevBuf<GroundState> d_state;
+    Pinned<GroundState[]> h_state;      // [0] read back, [1] the state uploaded
+    Pinned<int[]> h_words;              // [0..1] a compaction's flag and count, [2] the scans' flag, [3] the index sort's
+    DevBuf<unsigned> table;             // the generator's first table_words outputs (seed 12345)
+    size_t table_words = 0;
+    DevBuf<int2> hash;                  // touched entries of shuffled_indices_ (2 x table_words slots)
+    DevBuf<int4> tri;                   // per hypothesis: the sample and the sampler's status
+    DevBuf<float4> coef;
+    DevBuf<int> stat, cnt;
+    size_t hyp_cap = 0;
+    DevBuf<double> part;
+    DevBuf<unsigned> ticket;
+    std::vector<int> inject;            // ndt_ground_set_samples
+    ndt_ground_params prm{};            // of the last detect
+    ndt_ground_result res{};
+    bool valid = false;                 // a detect has run: the hooks and ndt_ground_cloud have something to read
+    int n_in = 0, n_clip = 0;
+};
+
 // Member order is part of the design: members are released in reverse order of declaration (delete c, the last step of
 // ndt_destroy, after it has joined the lane workers, synchronised the three streams and dropped the graph execs).  So
 // the main stream is declared before everything that is queued or released on it, capture_mu before the lane workers
@@ -386,6 +414,7 @@ struct ndt_ctx {
     bool have_result = false;
     IcpRun icp;
     GicpRun gicp;
+    GroundRun ground;
     // graph cache: a few captured chains (different slot counts / buffers), round-robin replacement
     static constexpr int kGraphKey = 23;
     static constexpr int kGraphCache = 64;

@@ -11,6 +11,7 @@
 #include "ndt_isc.h"
 #include "ndt_pgo.h"
 #include "ndt_map.h"
+#include "ndt_ground.h"
 
 namespace ndt {
 __global__ void k_minmax(const float4*, int, int, float*, int*, unsigned long long*, const GridHeader*, GridHeader*, float4*);
@@ -37,6 +38,15 @@ __global__ void k_sor_knn(const float4*, int, int, const GridHeader*, const int*
 __global__ void k_sor_stats(const float*, int, double, double*);
 __global__ void k_sor_keep(const float*, int, const double*, int*);
 __global__ void k_ror_keep(const float4*, int, double, int, const GridHeader*, const int*, const int*, const float4*, int*);
+__global__ void k_ground_clip_flags(const float4*, int, float, float, int*);
+__global__ void k_ground_origin(const int*, const int*, const int*, int, int*);
+template <int C>
+__global__ void k_ground_normals(const float4*, int, int, int, float, double, const GridHeader*, const int*, const int*, const float4*,
+                                 const int*, float4*, int*, int*);
+__global__ void k_ground_sample(const float4*, GroundState*, int, const unsigned*, int2*, int4*);
+__global__ void k_ground_score(const float4*, GroundState*, int, const int4*, float4*, int*, int*, double*, unsigned*);
+__global__ void k_ground_finish(const float4*, const int*, int, GroundState*, const int4*, const float4*, int*, int*);
+__global__ void k_ground_unmarked(const int*, int, int*);
 __global__ void k_downsample_finalize(const float4*, const int*, const GridHeader*, float4*);
 __global__ void k_fit_gather(const float4*, const int*, const int*, const int*, const int*, const int*, int, const GridHeader*, float4*,
                              int*, int*, int*);
