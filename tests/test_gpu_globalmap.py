@@ -353,6 +353,22 @@ def test_close_loops_from_a_store():
         same(xa.close_loops(None, poses, detect_args=detect, store=m, **refine))
 
 
+def test_add_strided_records(scene):
+    """ndt_map_add over 32-byte records with the intensity at float 4 (pcl::PointXYZI's layout, the padding poisoned)
+    stores the keyframe the packed (N, 4) call stores."""
+    cloud = scene["keyframes"][7]
+    assert len(cloud) == 300
+    wide = np.full((len(cloud), 8), np.nan, np.float32)
+    wide[:, :3] = cloud[:, :3]
+    wide[:, 4] = cloud[:, 3]
+    with xa.KeyframeMap() as m:
+        assert m.add(cloud) == 0
+        idx = C.c_int(-1)
+        assert m._lib.ndt_map_add(m._handle, _fp(wide), len(wide), 32, 4, C.byref(idx)) == _lib.NDT_OK and idx.value == 1
+        assert m.num_points == 600
+        assert same_bits(m.keyframe(0), cloud) and same_bits(m.keyframe(1), m.keyframe(0))
+
+
 # ---------------------------------------------------------------------------------------------- 7. argument errors
 def test_argument_errors(scene, store):
     """Plain argument checks: each is refused before anything is launched."""

@@ -164,6 +164,29 @@ def test_end_to_end_with_the_device_sampler(cf, xa):
     _defaults(cf)
 
 
+def test_detect_strided_records(cf, xa):
+    """ndt_ground_detect over 32-byte records with the intensity at float 4 (pcl::PointXYZI's layout, the padding
+    poisoned): the result record and the three clouds of the packed (N, 4) call."""
+    from xchu_slam_amd import ground
+    cloud = np.ascontiguousarray(gs.scene(0), F32)
+    wide = np.full((len(cloud), 8), np.nan, F32)
+    wide[:, :3] = cloud[:, :3]
+    wide[:, 4] = cloud[:, 3]
+    _defaults(cf)
+    packed = cf.detect_plane(cloud)
+    clouds = [getattr(packed, name)() for name in ("normal_ground", "ground", "no_ground")]
+    assert packed.found and all(len(c) > 0 for c in clouds)
+    rec = ground._record()
+    st = cf._lib.ndt_ground_detect(cf.ctx, C.byref(cf._gprm), wide.ctypes.data_as(C.POINTER(C.c_float)), len(wide), 32, 4, C.byref(rec))
+    assert st == 0
+    strided = ground.GroundResult(cf.registration, rec)
+    fields = ("found", "reason", "n_input", "n_clipped", "n_normal", "n_inliers", "iterations", "skipped", "k", "winner", "stream_fallbacks")
+    assert [getattr(strided, f) for f in fields] == [getattr(packed, f) for f in fields]
+    assert _same_bits(strided.coeffs, packed.coeffs)
+    for name, want in zip(("normal_ground", "ground", "no_ground"), clouds):
+        assert _same_bits(getattr(strided, name)(), want), name
+
+
 def test_literal_no_ground(cf):
     cloud = gs.scene(4)
     dev, ref = _compare(cf, "scene4-literal", cloud, literal_no_ground=True)

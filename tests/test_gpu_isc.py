@@ -128,6 +128,25 @@ def test_descriptors():
         assert np.array_equal(isc.getLastISCMONO(), R.calculate_isc(big))
 
 
+def test_descriptor_of_strided_records():
+    """ndt_isc_add over 32-byte records with the intensity at float 4 (pcl::PointXYZI's layout, the padding poisoned)
+    stores the bytes of the packed (N, 4) call."""
+    import xchu_slam_amd as xa
+    from xchu_slam_amd import _lib
+    cloud = np.ascontiguousarray(np.concatenate([route(0.0)["scans"][7][:300], EDGE_POINTS]), np.float32)
+    wide = np.full((len(cloud), 8), np.nan, np.float32)
+    wide[:, :3] = cloud[:, :3]
+    wide[:, 4] = cloud[:, 3]
+    pos = (C.c_double * 3)(1.0, 2.0, 0.0)
+    with xa.ISCGeneration() as isc:
+        i = isc.makeAndSavedec(cloud, (1.0, 2.0, 0.0))
+        idx = C.c_int(-1)
+        st = isc._lib.ndt_isc_add(isc._handle, wide.ctypes.data_as(C.POINTER(C.c_float)), len(wide), 32, 4, pos, C.byref(idx))
+        assert st == _lib.NDT_OK and idx.value == i + 1
+        assert np.count_nonzero(isc.descriptor(i)) > 50
+        assert np.array_equal(isc.descriptor(idx.value), isc.descriptor(i))
+
+
 def test_second_shape():
     """20 rings x 90 sectors over 60 m: a row / column mix-up cannot survive a non-square descriptor."""
     import xchu_slam_amd as xa

@@ -705,6 +705,29 @@ def test_ndt_cpu_update_voxel_grid(oracle):
     assert np.array_equal(g2.getFinalTransformation(), g.getFinalTransformation())
 
 
+def test_update_target_strided_records():
+    """ndt_update_target over 32-byte records (x, y, z first, the rest poisoned) gives the grid of the 16-byte call."""
+    import ctypes as C
+    pair = small_pair(seed=7)
+    first, more = pair.target[:1500], pair.target[1500:2400]
+    assert len(more) == 900
+    infos = []
+    for width in (4, 8):
+        rows = np.full((len(more), width), np.nan, np.float32)
+        rows[:, :3] = more[:, :3]
+        g = xa.NormalDistributionsTransform()
+        try:
+            g.setResolution(2.0)
+            g.setInputTarget(first)
+            st = g._lib.ndt_update_target(g._ctx, rows.ctypes.data_as(C.POINTER(C.c_float)), len(rows), width * 4)
+            assert st == 0
+            infos.append(g.grid_info())
+        finally:
+            g.close()
+    assert infos[0]["n_cloud"] > 0 and infos[0]["n_valid"] > 0
+    assert infos[1] == infos[0]
+
+
 def test_ndt_cpu_degenerate_voxels_never_rejected(oracle):
     """The ndt_cpu incremental quirk (a rejected voxel's points_per_voxel continues from -1 in updateVoxelGrid, so it
     can stay hidden from radiusSearch) needs a rejected voxel, and cpu::VoxelGrid cannot produce one: its covariance

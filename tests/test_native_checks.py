@@ -4,6 +4,8 @@
   angle_table_row: bit-exact on random angles (tests/native/angle_table_check.cpp).
 * the derivative passes' launch geometry and the two-level hand-off's grouping (csrc/ndt_geom.h, ndt_types.h), swept over
   CU counts, searches, pass options and source sizes around every threshold (tests/native/pass_geom_check.cpp).
+* the host steps every unit shares (csrc/ndt_geom.h): the strided-cloud packer, the xyzi layout rule and grid_for, also
+  under the host sanitizers (tests/native/cloud_pack_check.cpp).
 """
 import os
 import shutil
@@ -96,3 +98,19 @@ def test_pass_geometry_sweep(tmp_path):
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "mismatched: 0" in out.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_cloud_pack_and_grid_for(tmp_path):
+    """The host steps every unit shares (csrc/ndt_geom.h), tests/native/cloud_pack_check.cpp: pack_cloud4 equals the
+    literal strided loop for n = 0, 1, 5 and 1000 records of stride 12 (w = 1), 16 (intensity at float 3), 32 (at 4) and
+    32 (at 7, the record's last float); xyzi_layout_ok rejects (2,32), (3,12), (8,32) and (4,16) and accepts (3,16),
+    (4,32) and (7,32); grid_for at n = 0, 1, per, per + 1, cap * per and cap * per + 1.  Built and run a second time
+    with -fsanitize=address,undefined (a stand-alone host program: the record buffers end with their last record)."""
+    src = os.path.join(HERE, "native", "cloud_pack_check.cpp")
+    for tag, flags in (("plain", ["-O2"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
+        exe = tmp_path / ("cpc_" + tag)
+        subprocess.run(["g++", "-std=c++17", *flags, "-o", str(exe), src], check=True)
+        out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, tag + "\n" + out.stdout + out.stderr
+        assert "mismatched: 0" in out.stdout

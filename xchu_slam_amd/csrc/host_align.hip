@@ -426,14 +426,14 @@ ndt_status enqueue_source_order(ndt_ctx* c, const float T[16]) {
     Mat4f Tm;
     std::memcpy(Tm.m, T, sizeof(Tm.m));
     HIPCHK(c, hipMemsetAsync(c->s.radix_aux.p, 0, kRadixAuxWords * sizeof(int), c->stream.get()));
-    const int nb_keys = std::max(1, std::min(ceil_div(n, kBlock), 1024));
+    const int nb_keys = grid_for(n, kBlock, 1024);
     hipLaunchKernelGGL(k_src_keys, dim3(nb_keys), dim3(kBlock), 0, c->stream.get(), c->source.p, n, Tm, c->d_hdr.p, c->ord_k0.p, c->ord_v0.p,
                        c->s.radix_aux.p, c->s.radix_status.p, (int)radix_status_words(nb_sort));
     const int passes = radix_launch_passes(c);
     for (int pass = 0; pass < passes; ++pass)
         launch_radix_pass(c, main_lane(c), items, nb_sort, c->ord_k0.p, c->ord_v0.p, c->ord_k1.p, c->ord_v1.p, n, pass, c->d_hdr.p, c->d_hdr.p,
                           passes - 1);
-    hipLaunchKernelGGL(k_src_gather, dim3(std::max(1, std::min(ceil_div(n, kBlock), 2048))), dim3(kBlock), 0, c->stream.get(), c->source.p,
+    hipLaunchKernelGGL(k_src_gather, dim3(grid_for(n, kBlock, 2048)), dim3(kBlock), 0, c->stream.get(), c->source.p,
                        c->ord_v0.p, c->ord_v1.p, c->d_hdr.p, c->source_ord.p, n);
     HIPCHK(c, hipGetLastError());
     c->pass_src = c->source_ord.p;
@@ -749,7 +749,7 @@ ndt_status ndt_calculate_score(ndt_ctx* c, const float T[16], double* out) {
     if (!c->grid_valid) TRY(build_target(c));
     TRY(settle_build(c));
     TRY(flush_source(c));
-    const int nb = std::max(1, std::min(ceil_div(c->N, kBlock), 1024));
+    const int nb = grid_for(c->N, kBlock, 1024);
     TRY(ensure(c, c->score_part, nb));
     Mat4f Tm;
     for (int k = 0; k < 16; ++k) Tm.m[k] = T[k];

@@ -19,7 +19,7 @@ static ndt_status gicp_params_ok(ndt_ctx* c, const ndt_gicp_params& p) {
 }
 
 static void launch_cov(ndt_ctx* c, const float4* pts, int n, const ndt_gicp_params& p, const NNIndex& ix, double* out, double* raw) {
-    const int nb = std::max(1, std::min(ceil_div(n, kGicpTeams), kGicpCovMaxBlocks));
+    const int nb = grid_for(n, kGicpTeams, kGicpCovMaxBlocks);
     if (p.k_correspondences <= 20)
         hipLaunchKernelGGL(k_gicp_cov<20>, dim3(nb), dim3(kGicpBlock), 0, c->stream.get(), pts, n, p.k_correspondences, p.gicp_epsilon,
                            ix.hdr.p, ix.blk.p, ix.off.p, ix.pts.p, ix.idx.p, out, raw);
@@ -75,7 +75,7 @@ static ndt_status gicp_buffers(ndt_ctx* c) {
 
 static void launch_eval(ndt_ctx* c) {
     GicpRun& g = c->gicp;
-    const int nb = std::max(1, std::min(ceil_div(c->N, kGicpBlock), kGicpEvalBlocks));
+    const int nb = grid_for(c->N, kGicpBlock, kGicpEvalBlocks);
     hipLaunchKernelGGL(k_gicp_eval, dim3(nb), dim3(kGicpBlock), 0, c->stream.get(), c->source.p, c->N, g.d_state.p, g.match.p, g.qt.p,
                        g.gp.p, g.M.p, g.part.p, g.ticket.p + 32, g.d_hist.p);
 }
@@ -151,7 +151,7 @@ ndt_status ndt_gicp_align(ndt_ctx* c, const ndt_gicp_params* prm, const float gu
     gicp_set_final(s0);
     s0->phase = GICP_PAIRS;
     HIPCHK(c, hipMemcpyAsync(g.d_state.p, s0, sizeof(GicpState), hipMemcpyHostToDevice, c->stream.get()));
-    const int nbp = std::max(1, std::min(ceil_div(N, kGicpTeams), kGicpMaxBlocks));
+    const int nbp = grid_for(N, kGicpTeams, kGicpMaxBlocks);
     // the round budget: every block of a round that starts unfinished runs at least kGicpBlockEvals useful launches, or
     // ends a solve; an outer iteration takes at most one k_gicp_pairs and kGicpMaxEvals evaluations
     const long long iters = std::max(p.max_iter, 1);

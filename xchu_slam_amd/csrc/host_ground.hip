@@ -4,7 +4,9 @@
 // One detect is: tilt, clip flags, compaction (one read of the clipped count, which sizes the neighbour index's sort),
 // index build, k_ground_normals, compaction (its count stays on the device), tilt back, then chains of kGroundChain x
 // (k_ground_sample, k_ground_score) + k_ground_finish and one read of the state per chain.  The first chain ends almost
-// every scan (kGroundBatch, ndt_ground.h); a launch behind the end of the loop returns at its first load.
+// every scan (kGroundBatch, ndt_ground.h); a launch behind the end of the loop returns at its first load.  The
+// compactions are host_front_end.hip's enqueue_compact4 (with compact4_count where the host reads the count), the
+// clouds' VoxelGrid its voxel_downsample_dev.
 #include "ndt_host.h"
 
 namespace {
@@ -83,8 +85,6 @@ size_t first_table_words() {
     return words;
 }
 
-int blocks_for(long long n, int per, int cap) { return (int)std::max(1LL, std::min((n + per - 1) / per, (long long)cap)); }
-
 // the scan's RANSAC from its first sample: the state h_state[1] uploaded, the hypotheses and the hash cleared, chains of
 // launches until the loop has ended
 ndt_status ground_ransac(ndt_ctx* c, int m) {
@@ -93,7 +93,7 @@ ndt_status ground_ransac(ndt_ctx* c, int m) {
     HIPCHK(c, hipMemsetAsync(g.tri.p, 0xff, g.hyp_cap * sizeof(int4), st));  // every sample GROUND_SAMPLE_NONE
     HIPCHK(c, hipMemsetAsync(g.hash.p, 0xff, 2 * g.table_words * sizeof(int2), st));
     if (!g.inject.empty()) HIPCHK(c, hipMemcpyAsync(g.tri.p, g.inject.data(), g.inject.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    const int nbs = blocks_for(m, kGroundBlock, kGroundScoreMaxBlocks), nbf = blocks_for(m, kGroundBlock, 2048);
+    const int nbs = grid_for(m, kGroundBlock, kGroundScoreMaxBlocks), nbf = grid_for(m, kGroundBlock, 2048);
     const int max_batches = (int)(g.hyp_cap / kGroundBatch);
     bool done = false;
     for (int batch = 0; !done && batch < max_batches;) {
@@ -152,29 +152,23 @@ ndt_status ground_detect_dev(ndt_ctx* c, const ndt_ground_params* prm, const flo
     // ---- a. tilt, b. height clip (filter_node.cpp:106-115)
     Mat4f T, Tinv;
     tilt_matrices(p.tilt_deg, &T, &Tinv);
-    const int nb = blocks_for(N, kGroundBlock, 2048);
+    const int nb = grid_for(N, kGroundBlock, 2048);
     hipLaunchKernelGGL(k_transform_mat, dim3(ceil_div((long long)n, kBlock)), dim3(kBlock), 0, st, g.in.p, N, T, g.tilted.p);
     hipLaunchKernelGGL(k_ground_clip_flags, dim3(nb), dim3(kGroundBlock), 0, st, g.tilted.p, N, (float)(p.sensor_height + p.height_clip_range),
                        (float)(p.sensor_height - p.height_clip_range), g.flags.p);
-    TRY(enqueue_scan(c, main_lane(c), g.flags.p, N, nullptr, g.idx.p, &g.d_hdr.p->pad[1], g.d_hdr.p));
-    hipLaunchKernelGGL(k_compact4, dim3(nb), dim3(kBlock), 0, st, g.tilted.p, g.flags.p, g.idx.p, N, g.clip.p);
+    TRY(enqueue_compact4(c, g.tilted.p, g.flags.p, g.idx.p, N, g.clip.p, &g.d_hdr.p->pad[1], g.d_hdr.p));
     hipLaunchKernelGGL(k_ground_origin, dim3(nb), dim3(kGroundBlock), 0, st, g.flags.p, g.idx.p, (const int*)nullptr, N, g.clip_org.p);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(&g.h_words[0], &g.d_hdr.p->pad[0], 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    auto scan_failed = [&]() -> ndt_status {
-        (void)hipMemsetAsync(&g.d_hdr.p->pad[0], 0, sizeof(int), st);
-        return fail(c, NDT_EDEVICE, "ground: compaction scan: look-back timed out");
-    };
-    if (g.h_words[0]) return scan_failed();
+    const char* scan_timeout = "ground: compaction scan: look-back timed out";
+    TRY(compact4_count(c, g.d_hdr.p, &g.h_words[0], scan_timeout));
     const int m = g.h_words[1];
     r.n_clipped = m;
     g.n_clip = m;
     if (m == 0) return leave();
     // ---- c. normal filter (:72-101) over the clipped cloud's own neighbour index
-    const int nbm = blocks_for(m, kGroundBlock, 2048);
+    const int nbm = grid_for(m, kGroundBlock, 2048);
     const int k = std::min(p.normal_k, m);
-    const int nbq = blocks_for(m, kGroundTeams, kGroundNormalMaxBlocks);
+    const int nbq = grid_for(m, kGroundTeams, kGroundNormalMaxBlocks);
     const double cos_thr = std::cos(p.normal_filter_thresh * M_PI / 180.0);
     if (p.use_normal_filtering) {
         TRY(enqueue_nn_index(c, main_lane(c), g.clip.p, m, 1, kGroundCell, g.ix, true));
@@ -215,9 +209,8 @@ ndt_status ground_detect_dev(ndt_ctx* c, const ndt_ground_params* prm, const flo
     s0->k = 1.0;
     s0->winner[0] = s0->winner[1] = s0->winner[2] = -1;
     HIPCHK(c, hipMemcpyAsync(g.d_state.p, s0, sizeof(GroundState), hipMemcpyHostToDevice, st));
-    TRY(enqueue_scan(c, main_lane(c), g.flags.p, m, nullptr, g.idx.p, &g.d_state.p->n_normal, g.d_hdr.p));
     HIPCHK(c, hipMemsetAsync(g.nrm_t.p, 0, (size_t)m * sizeof(float4), st));  // what lies past the kept count is moved back too
-    hipLaunchKernelGGL(k_compact4, dim3(nbm), dim3(kBlock), 0, st, g.clip.p, g.flags.p, g.idx.p, m, g.nrm_t.p);
+    TRY(enqueue_compact4(c, g.clip.p, g.flags.p, g.idx.p, m, g.nrm_t.p, &g.d_state.p->n_normal, g.d_hdr.p));
     hipLaunchKernelGGL(k_ground_origin, dim3(nbm), dim3(kGroundBlock), 0, st, g.flags.p, g.idx.p, g.clip_org.p, m, g.nrm_org.p);
     // the cloud after the filters moved back by T^-1 (:121): /normal_ground_points, and what RANSAC runs over
     hipLaunchKernelGGL(k_transform_mat, dim3(ceil_div((long long)m, kBlock)), dim3(kBlock), 0, st, g.nrm_t.p, m, Tinv, g.nrm.p);
@@ -238,7 +231,10 @@ ndt_status ground_detect_dev(ndt_ctx* c, const ndt_ground_params* prm, const flo
         HIPCHK(c, hipMemcpyAsync(g.d_state.p, s0, sizeof(GroundState), hipMemcpyHostToDevice, st));
         TRY(ground_ransac(c, m));
     }
-    if (g.h_words[2]) return scan_failed();
+    if (g.h_words[2]) {  // the second compaction's scan, whose flag came back with the state
+        (void)hipMemsetAsync(&g.d_hdr.p->pad[0], 0, sizeof(int), st);
+        return fail(c, NDT_EDEVICE, scan_timeout);
+    }
     if (g.h_words[3]) return fail(c, NDT_EDEVICE, "ground: neighbour index sort: radix look-back timed out");
     const GroundState& s = g.h_state[0];
     r.found = s.found;
@@ -268,18 +264,11 @@ ndt_status ground_cloud_dev(ndt_ctx* c, int which, const float4** src, size_t* c
     } else if (r.found) {
         const bool gr = which == NDT_GROUND_CLOUD_GROUND;
         const int n = gr ? r.n_normal : r.n_input;
-        const int nb = blocks_for(n, kGroundBlock, 2048);
+        const int nb = grid_for(n, kGroundBlock, 2048);
         if (!gr) hipLaunchKernelGGL(k_ground_unmarked, dim3(nb), dim3(kGroundBlock), 0, st, g.mark.p, n, g.flags.p);
         const int* flags = gr ? g.gflag.p : g.flags.p;
-        TRY(enqueue_scan(c, main_lane(c), flags, n, nullptr, g.idx.p, &g.d_hdr.p->pad[1], g.d_hdr.p));
-        hipLaunchKernelGGL(k_compact4, dim3(nb), dim3(kBlock), 0, st, gr ? g.nrm.p : g.in.p, flags, g.idx.p, n, g.cloud.p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(&g.h_words[0], &g.d_hdr.p->pad[0], 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (g.h_words[0]) {
-            (void)hipMemsetAsync(&g.d_hdr.p->pad[0], 0, sizeof(int), st);
-            return fail(c, NDT_EDEVICE, "ground: cloud compaction scan: look-back timed out");
-        }
+        TRY(enqueue_compact4(c, gr ? g.nrm.p : g.in.p, flags, g.idx.p, n, g.cloud.p, &g.d_hdr.p->pad[1], g.d_hdr.p));
+        TRY(compact4_count(c, g.d_hdr.p, &g.h_words[0], "ground: cloud compaction scan: look-back timed out"));
         *src = g.cloud.p;
         *count = (size_t)g.h_words[1];
     }
@@ -292,6 +281,20 @@ ndt_status ground_cloud_dev(ndt_ctx* c, int which, const float4** src, size_t* c
         return rs;
     }
     return NDT_OK;
+}
+
+// ndt_ground_cloud / ndt_ground_cloud_device: up to cap points of that cloud to out4, host or device memory by the copy's
+// kind; synchronises
+ndt_status ground_cloud_out(ndt_ctx* c, int which, float* out4, size_t cap, size_t* n_out, hipMemcpyKind kind) {
+    if (!c || !n_out || (cap && !out4)) return fail(c, NDT_EINVAL, "bad ground cloud args");
+    TRY(set_dev(c));
+    const float4* src = nullptr;
+    const ndt_status rs = ground_cloud_dev(c, which, &src, n_out);
+    if (rs != NDT_OK && rs != NDT_EOVERFLOW) return rs;
+    const size_t k = std::min(cap, *n_out);
+    if (k) HIPCHK(c, hipMemcpyAsync(out4, src, k * sizeof(float4), kind, c->stream.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
+    return rs;
 }
 
 }  // namespace
@@ -327,17 +330,11 @@ ndt_status ndt_ground_detect_device(ndt_ctx* c, const ndt_ground_params* prm, co
 
 ndt_status ndt_ground_detect(ndt_ctx* c, const ndt_ground_params* prm, const float* xyzi, size_t n, size_t stride_bytes, int intensity_offset,
                              ndt_ground_result* result) {
-    if (!c || !result || (n && !xyzi) || stride_bytes < 16 || intensity_offset < 3 || (size_t)intensity_offset * 4 + 4 > stride_bytes ||
-        n > 0x7fffffffULL)
+    if (!c || !result || (n && !xyzi) || !xyzi_layout_ok(stride_bytes, intensity_offset) || n > 0x7fffffffULL)
         return fail(c, NDT_EINVAL, "bad ground args");
     TRY(set_dev(c));
     if (n == 0) return ground_detect_dev(c, prm, nullptr, 0, result);
-    std::vector<float4> tmp(n);
-    const char* base = reinterpret_cast<const char*>(xyzi);
-    for (size_t i = 0; i < n; ++i) {
-        const float* f = reinterpret_cast<const float*>(base + i * stride_bytes);
-        tmp[i] = make_float4(f[0], f[1], f[2], f[intensity_offset]);
-    }
+    const std::vector<float> tmp = pack_cloud4(xyzi, n, stride_bytes, intensity_offset);
     TRY(ensure(c, c->ground.in, n));
     HIPCHK(c, hipMemcpyAsync(c->ground.in.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream.get()));
     HIPCHK(c, hipStreamSynchronize(c->stream.get()));  // tmp goes with this scope
@@ -345,29 +342,11 @@ ndt_status ndt_ground_detect(ndt_ctx* c, const ndt_ground_params* prm, const flo
 }
 
 ndt_status ndt_ground_cloud_device(ndt_ctx* c, int which, float* d_out4, size_t cap, size_t* n_out) {
-    if (!c || !n_out || (cap && !d_out4)) return fail(c, NDT_EINVAL, "bad ground cloud args");
-    TRY(set_dev(c));
-    const float4* src = nullptr;
-    const ndt_status rs = ground_cloud_dev(c, which, &src, n_out);
-    if (rs != NDT_OK && rs != NDT_EOVERFLOW) return rs;
-    const size_t k = std::min(cap, *n_out);
-    if (k) HIPCHK(c, hipMemcpyAsync(d_out4, src, k * sizeof(float4), hipMemcpyDeviceToDevice, c->stream.get()));
-    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
-    return rs;
+    return ground_cloud_out(c, which, d_out4, cap, n_out, hipMemcpyDeviceToDevice);
 }
 
 ndt_status ndt_ground_cloud(ndt_ctx* c, int which, float* out4, size_t cap, size_t* n_out) {
-    if (!c || !n_out || (cap && !out4)) return fail(c, NDT_EINVAL, "bad ground cloud args");
-    TRY(set_dev(c));
-    const float4* src = nullptr;
-    const ndt_status rs = ground_cloud_dev(c, which, &src, n_out);
-    if (rs != NDT_OK && rs != NDT_EOVERFLOW) return rs;
-    const size_t k = std::min(cap, *n_out);
-    if (k) {
-        HIPCHK(c, hipMemcpyAsync(out4, src, k * sizeof(float4), hipMemcpyDeviceToHost, c->stream.get()));
-        HIPCHK(c, hipStreamSynchronize(c->stream.get()));
-    }
-    return rs;
+    return ground_cloud_out(c, which, out4, cap, n_out, hipMemcpyDeviceToHost);
 }
 
 ndt_status ndt_filter_ground_scan(ndt_ctx* c, const ndt_filter_params* fprm, const ndt_ground_params* gprm, const float* d_in4, size_t n,

@@ -55,7 +55,7 @@ ndt_status ndt_icp_align(ndt_ctx* c, const ndt_icp_params* prm, const float gues
     TRY(make_run_state(c, c->icp.d_state, c->icp.d_hist, kIcpMaxHistory, c->icp.h_state, hipHostMallocCoherent,
                        "ICP state allocation failed"));
     const int N = c->N;
-    const int nb = std::max(1, std::min(ceil_div(N, kIcpTeams), kIcpMaxBlocks));
+    const int nb = grid_for(N, kIcpTeams, kIcpMaxBlocks);
     TRY(ensure(c, c->icp.x, N)); TRY(ensure(c, c->icp.match, N)); TRY(ensure(c, c->icp.d2, N));
     TRY(ensure(c, c->icp.part, (size_t)kIcpSums * kIcpMaxBlocks));
     if (!c->icp.ticket.p) {

@@ -139,8 +139,7 @@ ndt_status ndt_isc_create(ndt_ctx* c, const ndt_isc_params* prm, ndt_isc** out) 
 
 void ndt_isc_destroy(ndt_isc* h) {
     if (!h) return;
-    (void)hipSetDevice(h->c->device);
-    (void)hipStreamSynchronize(h->c->stream.get());  // queued launches still read the database
+    drain_for_destroy(h->c);
     delete h;
 }
 
@@ -156,17 +155,11 @@ ndt_status ndt_isc_add_device(ndt_isc* h, const float* d_xyzi4, size_t n, const 
 ndt_status ndt_isc_add(ndt_isc* h, const float* xyzi, size_t n, size_t stride_bytes, int intensity_offset, const double pos[3], int* index) {
     if (!h) return NDT_EINVAL;
     ndt_ctx* c = h->c;
-    if (!pos || n > 0x7fffffffULL ||
-        (n && (!xyzi || stride_bytes < 16 || intensity_offset < 3 || (size_t)intensity_offset * 4 + 4 > stride_bytes)))
+    if (!pos || n > 0x7fffffffULL || (n && (!xyzi || !xyzi_layout_ok(stride_bytes, intensity_offset))))
         return fail(c, NDT_EINVAL, "bad cloud arguments");
     TRY(set_dev(c));
     TRY(ensure(c, h->pts, n));
-    std::vector<float4> tmp(n);
-    const char* base = reinterpret_cast<const char*>(xyzi);
-    for (size_t i = 0; i < n; ++i) {
-        const float* f = reinterpret_cast<const float*>(base + i * stride_bytes);
-        tmp[i] = make_float4(f[0], f[1], f[2], f[intensity_offset]);
-    }
+    const std::vector<float> tmp = pack_cloud4(xyzi, n, stride_bytes, intensity_offset);
     if (n) HIPCHK(c, hipMemcpyAsync(h->pts.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream.get()));
     HIPCHK(c, hipStreamSynchronize(c->stream.get()));  // tmp is free; the previous add has read h->pts
     return isc_add_points(h, h->pts.p, n, pos, index);

@@ -91,7 +91,7 @@ ndt_status enqueue_nn_index(ndt_ctx* c, Lane L, const float4* pts, int n, int de
     TRY(enqueue_bin_and_sort(c, L, pts, n, dense, ix.hdr.p, cell, 1));
     TRY(ensure(c, ix.pts, std::max(n, 1))); TRY(ensure(c, ix.keys, std::max(n, 1))); TRY(ensure(c, ix.start, (size_t)n + 1));
     if (want_idx) TRY(ensure(c, ix.idx, std::max(n, 1)));
-    const int nb = std::max(1, std::min(ceil_div(n, kBlock), 4096));
+    const int nb = grid_for(n, kBlock, 4096);
     hipLaunchKernelGGL(k_fit_gather, dim3(nb), dim3(kBlock), 0, L.st, pts, L.s.k0.p, L.s.k1.p, L.s.v0.p, L.s.v1.p,
                        L.s.seg_start.p, n, ix.hdr.p, ix.pts.p, ix.keys.p, ix.start.p, want_idx ? ix.idx.p : nullptr);
     // occupied blocks: flags -> exclusive scan -> block table + 513 cell offsets per occupied block
@@ -192,7 +192,7 @@ static ndt_status fitness_enqueue(ndt_ctx* c, const float* T, double max_range, 
         // 16-lane team per query; the grid capped at 32 Ki workgroups (measured caps 8192 / 2048 / 1024 / 512 of 256-thread
         // workgroups: 89.4 / 85.9 / 90.7 / 128.9 us on C3)
         constexpr int grid_cap = 8192 * (256 / kFitBlock);
-        const int nb = std::max(1, std::min(ceil_div(N, kFitBlock / kFitTeam), grid_cap));
+        const int nb = grid_for(N, kFitBlock / kFitTeam, grid_cap);
         const int ngrp = ceil_div(nb, kFitGroup);
         TRY(ensure(c, c->fit_sum, nb + ngrp)); TRY(ensure(c, c->fit_cnt, nb + ngrp)); TRY(ensure(c, c->fit_d2, N));
         const size_t n_ticket = (size_t)kFitTicketStride * (1 + ngrp);
@@ -335,9 +335,8 @@ ndt_status ndt_keyframe_insert_async(ndt_ctx* c, const float T[16], const float*
         HIPCHK(c, hipStreamWaitEvent(L.st, ev_main, 0));
         TRY(ensure(c, c->lanes.ins_tr, n)); TRY(ensure(c, c->lanes.ins_ds, n));
         hipLaunchKernelGGL(k_transform_mat, dim3(ceil_div((long long)n, kBlock)), dim3(kBlock), 0, L.st, scan, (int)n, Tm, c->lanes.ins_tr.p);
-        TRY(enqueue_bin_and_sort(c, L, c->lanes.ins_tr.p, (int)n, 1, c->lanes.d_hdr_ins.p, leaf));
-        TRY(enqueue_downsample_finalize(c, L, c->lanes.d_hdr_ins.p, c->lanes.ins_tr.p, (int)n, c->lanes.ins_ds.p));
-        hipLaunchKernelGGL(k_append2, dim3(std::max(1, std::min(ceil_div((long long)n, kBlock), 1024))), dim3(kBlock), 0, L.st,
+        TRY(enqueue_voxel_grid(c, L, c->lanes.ins_tr.p, (int)n, leaf, c->lanes.d_hdr_ins.p, c->lanes.ins_ds.p));
+        hipLaunchKernelGGL(k_append2, dim3(grid_for((long long)n, kBlock, 1024)), dim3(kBlock), 0, L.st,
                            c->lanes.ins_ds.p, c->lanes.ins_tr.p, (int)n, c->lanes.d_hdr_ins.p, dst_a, dst_b);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(&c->h_async->ins_hdr, c->lanes.d_hdr_ins.p, sizeof(GridHeader), hipMemcpyDeviceToHost, L.st));

@@ -65,8 +65,7 @@ ndt_status ndt_map_create(ndt_ctx* c, ndt_map** out) {
 
 void ndt_map_destroy(ndt_map* m) {
     if (!m) return;
-    (void)hipSetDevice(m->c->device);
-    (void)hipStreamSynchronize(m->c->stream.get());  // queued launches still read the arena and the table
+    drain_for_destroy(m->c);
     delete m;
 }
 
@@ -96,18 +95,12 @@ ndt_status ndt_map_reserve(ndt_map* m, long long points) {
 ndt_status ndt_map_add(ndt_map* m, const float* xyzi, size_t n, size_t stride_bytes, int intensity_offset, int* index) {
     if (!m) return NDT_EINVAL;
     ndt_ctx* c = m->c;
-    if (n && (!xyzi || stride_bytes < 16 || intensity_offset < 3 || (size_t)intensity_offset * 4 + 4 > stride_bytes))
-        return fail(c, NDT_EINVAL, "bad cloud arguments");
+    if (n && (!xyzi || !xyzi_layout_ok(stride_bytes, intensity_offset))) return fail(c, NDT_EINVAL, "bad cloud arguments");
     TRY(map_can_add(m, n));
     TRY(set_dev(c));
     if (n) {
         TRY(map_reserve(m, m->used + n));
-        std::vector<float4> tmp(n);
-        const char* base = reinterpret_cast<const char*>(xyzi);
-        for (size_t i = 0; i < n; ++i) {
-            const float* f = reinterpret_cast<const float*>(base + i * stride_bytes);
-            tmp[i] = make_float4(f[0], f[1], f[2], f[intensity_offset]);
-        }
+        const std::vector<float> tmp = pack_cloud4(xyzi, n, stride_bytes, intensity_offset);
         HIPCHK(c, hipMemcpyAsync(m->arena.p + m->used, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream.get()));
         HIPCHK(c, hipStreamSynchronize(c->stream.get()));  // tmp goes on return
     }

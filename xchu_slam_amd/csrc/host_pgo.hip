@@ -76,8 +76,7 @@ ndt_status ndt_pgo_create(ndt_ctx* c, const ndt_pgo_params* prm, ndt_pgo** out) 
 
 void ndt_pgo_destroy(ndt_pgo* g) {
     if (!g) return;
-    (void)hipSetDevice(g->c->device);
-    (void)hipStreamSynchronize(g->c->stream.get());
+    drain_for_destroy(g->c);
     delete g;
 }
 

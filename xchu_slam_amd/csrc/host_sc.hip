@@ -129,8 +129,7 @@ ndt_status ndt_sc_create(ndt_ctx* c, const ndt_sc_params* prm, ndt_sc** out) {
 
 void ndt_sc_destroy(ndt_sc* sc) {
     if (!sc) return;
-    (void)hipSetDevice(sc->c->device);
-    (void)hipStreamSynchronize(sc->c->stream.get());  // queued launches still read the database
+    drain_for_destroy(sc->c);
     delete sc;
 }
 

@@ -1,5 +1,6 @@
 // host_sort.hip — sort / scan plumbing of the host side: the single-pass scans, the radix passes and the
-// bin-and-sort sequence every binning of the library runs (target build, VoxelGrid, nearest-neighbour index).
+// bin-and-sort sequence every binning of the library runs (target build, VoxelGrid, nearest-neighbour index), and
+// VoxelGrid's enqueue half (enqueue_voxel_grid).
 #include "ndt_host.h"
 
 namespace ndt::host {
@@ -79,7 +80,7 @@ void note_grid_width(ndt_ctx* c, long long cells, int dense) {
 ndt_status enqueue_bin_and_sort(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, GridHeader* h, float leaf, int layout,
                                 int binning, int2* cloud_span, int passes) {
     if (&L.s == &c->s && !cloud_span) c->inc_ok = false;  // another main-stream sort overwrites the target's sorted keys
-    const int nb_mm = std::max(1, std::min(ceil_div(n, 4 * kBlock), 1024));  // k_minmax: four points per thread per round
+    const int nb_mm = grid_for(n, 4 * kBlock, 1024);  // k_minmax: four points per thread per round
     TRY(ensure(c, L.s.mm, (size_t)nb_mm * 7));
     // small sorts (fewer 4096-key tiles than CUs) use 1024-key tiles: 4x the workgroups, a quarter of the latency
     const int items = radix_items(c, n);
@@ -94,7 +95,7 @@ ndt_status enqueue_bin_and_sort(ndt_ctx* c, Lane L, const float4* pts, int n, in
     // min/max partials (and the digit histograms cleared), then keys: every keys workgroup derives the header itself
     hipLaunchKernelGGL(k_minmax, dim3(nb_mm), dim3(kBlock), 0, L.st, pts, n, dense, L.s.mm.p, L.s.radix_aux.p,
                        cloud_span ? c->d_clk.p + 3 : nullptr, nullptr, nullptr, nullptr);
-    const int nb_keys = std::max(1, std::min(ceil_div(n, 4 * kBlock), 512));
+    const int nb_keys = grid_for(n, 4 * kBlock, 512);
     hipLaunchKernelGGL(k_keys, dim3(nb_keys), dim3(kBlock), 0, L.st, pts, n, dense, L.s.mm.p, nb_mm, h, leaf, c->prm.min_points_per_voxel,
                        c->prm.min_covar_eigvalue_mult, layout, binning, L.s.k0.p, L.s.v0.p, L.s.radix_aux.p, L.s.radix_status.p,
                        (int)radix_status_words(nb_sort), cloud_span ? c->grid.p : nullptr, (long long)c->grid.cap, cloud_span ? c->table.p : nullptr,
@@ -113,10 +114,13 @@ ndt_status enqueue_bin_and_sort(ndt_ctx* c, Lane L, const float4* pts, int n, in
     return NDT_OK;
 }
 
-// VoxelGrid means of the points binned on h: gather into voxel order, then one serial sum per voxel
-ndt_status enqueue_downsample_finalize(ndt_ctx* c, Lane L, const GridHeader* h, const float4* in, int n, float4* out) {
+// pcl::VoxelGrid's enqueue half, on the lane's stream, scratch and header h: the n points binned and sorted by leaf, then
+// the voxel means into out: gather into voxel order, one serial sum per voxel.  h ends with n_leaves, overflow and the
+// sort's look-back flag (pad[0]) for the caller to read back.
+ndt_status enqueue_voxel_grid(ndt_ctx* c, Lane L, const float4* in, int n, float leaf, GridHeader* h, float4* out) {
+    TRY(enqueue_bin_and_sort(c, L, in, n, 1, h, leaf));
     TRY(ensure(c, L.s.sorted_pts, std::max(n, 1)));
-    const int nb = std::max(1, std::min(ceil_div(n, 4 * kBlock), 2048));  // four points per thread per round
+    const int nb = grid_for(n, 4 * kBlock, 2048);  // four points per thread per round
     hipLaunchKernelGGL(k_sorted_gather, dim3(nb), dim3(kBlock), 0, L.st, in, L.s.v0.p, L.s.v1.p, h, L.s.sorted_pts.p, n);
     hipLaunchKernelGGL(k_downsample_finalize, dim3(std::max(1, ceil_div(n, kBlock))), dim3(kBlock), 0, L.st, L.s.sorted_pts.p,
                        L.s.seg_start.p, h, out);

@@ -77,7 +77,7 @@ ndt_status enqueue_target_append(ndt_ctx* c, int n_old, int n_new, const float4*
     float4* copy_to = new_src ? const_cast<float4*>(c->target_ptr) + n_old : nullptr;
     const float4* pts_new = new_src ? new_src : c->target_ptr + n_old;
     const int nq = std::max(n_new, 1);
-    const int nb_mm = std::max(1, std::min(ceil_div(nq, 4 * kBlock), 1024));
+    const int nb_mm = grid_for(nq, 4 * kBlock, 1024);
     TRY(ensure(c, Q.s.mm, (size_t)nb_mm * 7));
     const int items = radix_items(c, nq);
     const int nb_sort = std::max(1, ceil_div(nq, kBlock * items));
@@ -172,12 +172,7 @@ ndt_status settle_build(ndt_ctx* c) {
 
 ndt_status upload_points(ndt_ctx* c, DevBuf<float4>& dst, const float* xyz, size_t n, size_t stride_bytes) {
     TRY(ensure(c, dst, n));
-    std::vector<float4> tmp(n);
-    const char* base = reinterpret_cast<const char*>(xyz);
-    for (size_t i = 0; i < n; ++i) {
-        const float* f = reinterpret_cast<const float*>(base + i * stride_bytes);
-        tmp[i] = make_float4(f[0], f[1], f[2], 1.0f);
-    }
+    const std::vector<float> tmp = pack_cloud4(xyz, n, stride_bytes, -1);
     if (n) HIPCHK(c, hipMemcpyAsync(dst.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream.get()));
     HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     return NDT_OK;
@@ -208,12 +203,7 @@ static ndt_status append_target(ndt_ctx* c, const float4* d_new, const float* h_
     if (d_new) {
         HIPCHK(c, hipMemcpyAsync(c->target.p + m0, d_new, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream.get()));
     } else {
-        std::vector<float4> tmp(n);
-        const char* base = reinterpret_cast<const char*>(h_new);
-        for (size_t i = 0; i < n; ++i) {
-            const float* f = reinterpret_cast<const float*>(base + i * stride_bytes);
-            tmp[i] = make_float4(f[0], f[1], f[2], 1.0f);
-        }
+        const std::vector<float> tmp = pack_cloud4(h_new, n, stride_bytes, -1);
         HIPCHK(c, hipMemcpyAsync(c->target.p + m0, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream.get()));
         HIPCHK(c, hipStreamSynchronize(c->stream.get()));
     }

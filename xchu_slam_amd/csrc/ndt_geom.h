@@ -1,10 +1,15 @@
 // ndt_geom.h — launch geometry of the derivative passes as pure host functions of a small POD (PassShape): which
 // k_pass_direct / k_pass_lead instantiation a context launches, over how many workgroups, with how many points per
 // workgroup and tile, and how a grid's partials are summed (one level, or the two-level hand-off of pass_handoff).
+// Beside it the two host steps every unit shares: the grid size of a capped launch (grid_for) and the packing of a
+// caller's strided cloud into 4-float points (pack_cloud4, xyzi_layout_ok).
 // No HIP dependency: host_align.hip launches through it, ndt_pass_geometry reports from it, and
-// tests/native/pass_geom_check.cpp sweeps it with a host compiler.
+// tests/native/pass_geom_check.cpp and cloud_pack_check.cpp run it with a host compiler.
 #pragma once
 #include <algorithm>
+#include <cstddef>
+#include <cstring>
+#include <vector>
 #ifndef __host__  // a host compiler: ndt_types.h marks its constexpr helpers for both sides
 #define __host__
 #define __device__
@@ -21,8 +26,31 @@ struct PassShape {
     int n_cu, N, M, search, min_points_per_voxel, ppt;
 };
 
+// Workgroups of a grid-stride launch over n items, `per` items per workgroup and round: at least one, at most cap
+inline int grid_for(long long n, long long per, int cap) { return (int)std::max(1LL, std::min((n + per - 1) / per, (long long)cap)); }
+
 // k_pass_radius: one point per thread, grid-stride, at most 2048 workgroups
-inline int pass_blocks(int n) { return std::max(1, std::min(ceil_div(n, kBlock), 2048)); }
+inline int pass_blocks(int n) { return grid_for(n, kBlock, 2048); }
+
+// The layout rule of the C-ABI's xyzi clouds: records of at least four floats, the intensity behind xyz and inside the record
+inline bool xyzi_layout_ok(size_t stride_bytes, int intensity_offset) {
+    return stride_bytes >= 16 && intensity_offset >= 3 && (size_t)intensity_offset * 4 + 4 <= stride_bytes;
+}
+
+// n records of stride_bytes, each starting with x, y, z, packed into 4-float points (x, y, z, w): w the record's float
+// at intensity_offset, or 1.0f when intensity_offset < 0 (an xyz cloud).  Only packs: the upload and its synchronise
+// stay with the caller, which keeps the vector until then.
+inline std::vector<float> pack_cloud4(const void* records, size_t n, size_t stride_bytes, int intensity_offset) {
+    std::vector<float> out(4 * n);
+    const char* base = static_cast<const char*>(records);
+    for (size_t i = 0; i < n; ++i) {
+        const char* rec = base + i * stride_bytes;
+        std::memcpy(&out[4 * i], rec, 3 * sizeof(float));
+        if (intensity_offset < 0) out[4 * i + 3] = 1.0f;
+        else std::memcpy(&out[4 * i + 3], rec + (size_t)intensity_offset * sizeof(float), sizeof(float));
+    }
+    return out;
+}
 
 // The point count a pass chain's launch geometry is built for: the scan's size rounded up to 1/64 of its power of two
 // (<= ~1.6 % more points per workgroup), at least a multiple of 256.  The pass kernels take the real count from the align state, so one

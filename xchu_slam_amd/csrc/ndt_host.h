@@ -530,6 +530,12 @@ inline ndt_status set_dev(ndt_ctx* c) {
     return NDT_OK;
 }
 
+// ahead of a handle's delete (ndt_sc, ndt_isc, ndt_pgo, ndt_map): launches queued on its ctx's stream still read its buffers
+inline void drain_for_destroy(const ndt_ctx* c) {
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream.get());
+}
+
 // what every registration call needs: a target and a non-empty source
 inline ndt_status need_target_and_source(ndt_ctx* c) {
     if (!c->has_target) return fail(c, NDT_ENOTARGET, "no input target");
@@ -548,7 +554,7 @@ int radix_launch_passes(const ndt_ctx* c);
 void note_grid_width(ndt_ctx* c, long long cells, int dense);
 ndt_status enqueue_bin_and_sort(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, GridHeader* h, float leaf, int layout = 0,
                                 int binning = 0, int2* cloud_span = nullptr, int passes = 4);
-ndt_status enqueue_downsample_finalize(ndt_ctx* c, Lane L, const GridHeader* h, const float4* in, int n, float4* out);
+ndt_status enqueue_voxel_grid(ndt_ctx* c, Lane L, const float4* in, int n, float leaf, GridHeader* h, float4* out);
 // host_target.hip
 ndt_status build_target(ndt_ctx* c);
 ndt_status rerun_build(ndt_ctx* c, int berr);
@@ -581,7 +587,10 @@ ndt_status ensure_fit_index(ndt_ctx* c);
 ndt_status target_nn_index(ndt_ctx* c, const char* prefix);
 ndt_status check_index_sort(ndt_ctx* c, const NNIndex& ix, const char* prefix);
 // host_front_end.hip
-ndt_status voxel_downsample_dev(ndt_ctx* c, const float4* in, size_t n, float leaf, float4* out, size_t* n_out);
+ndt_status voxel_downsample_dev(ndt_ctx* c, const float4* in, size_t n, float leaf, float4* out, size_t* n_out,
+                                const char* what = "voxel downsample");
+ndt_status enqueue_compact4(ndt_ctx* c, const float4* in, const int* flags, int* idx, int n, float4* out, int* d_count, GridHeader* herr);
+ndt_status compact4_count(ndt_ctx* c, GridHeader* herr, int* h_words, const char* timeout_text);
 // host_sc.hip
 ndt_status reserve_slots(ndt_ctx* c, SlotArrays& a, size_t size, size_t need, std::initializer_list<size_t> slot_bytes, const char* what);
 
