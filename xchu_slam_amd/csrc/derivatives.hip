@@ -515,7 +515,7 @@ __device__ __forceinline__ void pass_direct_impl(const float4* __restrict__ src,
     const int pass_idx = st->n_passes;
     if (pass_idx >= kMaxHistory) ts = nullptr;
     if (ts && stamp0) ts[kTsStride * pass_idx] = t_entry;
-    __shared__ double red[NW * kNumAcc];
+    __shared__ double red[NW * kRedStride];
     double acc[kSplitAcc];
 #pragma unroll
     for (int v = 0; v < kSplitAcc; ++v) acc[v] = 0.0;
@@ -676,7 +676,7 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
         }
     }
     if (!body) return;
-    __shared__ double redw[NW * kNumAcc];
+    __shared__ double redw[NW * kRedStride];
     double acc[kSplitAcc];
 #pragma unroll
     for (int v = 0; v < kSplitAcc; ++v) acc[v] = 0.0;

@@ -4,6 +4,7 @@
 #include "ndt_types.h"
 #include "ndt_linalg.h"
 #include "ndt_pair.h"
+#include "ndt_rstree.h"
 
 namespace ndt {
 
@@ -139,8 +140,9 @@ template <int CTRL>
 __device__ __forceinline__ double dpp_d(double v) {
     unsigned lo, hi;
     split_d(v, lo, hi);
-    lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, CTRL, 0xf, 0xf, false);
-    hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, CTRL, 0xf, 0xf, false);
+    // every lane of these controls reads a lane of its own row: no lane keeps the old value (bound_ctrl: none is set up)
+    lo = (unsigned)__builtin_amdgcn_mov_dpp((int)lo, CTRL, 0xf, 0xf, true);
+    hi = (unsigned)__builtin_amdgcn_mov_dpp((int)hi, CTRL, 0xf, 0xf, true);
     return join_d(lo, hi);
 }
 template <int M>
@@ -206,30 +208,59 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[NV], double* re
 __host__ __device__ constexpr int split_lo_term(int k) { return k < 4 ? k : 7 + 6 * ((k - 4) / 3) + (k - 4) % 3; }
 __host__ __device__ constexpr int split_hi_term(int k) { return k < 3 ? 4 + k : (k == 3 ? 43 : 10 + 6 * ((k - 4) / 3) + (k - 4) % 3); }
 constexpr int kSplitAcc = 22;
+// the same map without branches on k (a lane of block_reduce_store_split looks its own term up): (k - 4) / 3 as a
+// multiplication, checked below against the two functions above for every k
+__host__ __device__ constexpr int split_term(bool hi, int k) {
+    const int r = ((k - 4) * 11) >> 5;
+    const int body = (hi ? 10 : 7) + (k - 4) + 3 * r;
+    const int head = hi ? (k == 3 ? 43 : 4 + k) : k;
+    return k < 4 ? head : body;
+}
+constexpr bool split_term_matches() {
+    for (int k = 0; k < kSplitAcc; ++k)
+        if (split_term(false, k) != split_lo_term(k) || split_term(true, k) != split_hi_term(k)) return false;
+    return true;
+}
+static_assert(split_term_matches(), "split_term restates split_lo_term / split_hi_term");
+
+// The register exchanges of rs22_reduce (ndt_rstree.h) on one lane
+struct RsLaneOps {
+    using T = double;
+    int lane;
+    __device__ __forceinline__ double swap16(double A, double B) const { return swap_add_d<16>(A, B); }
+    template <int M>
+    __device__ __forceinline__ double xchg(double A, double B) const {
+        const bool hi = (lane & M) != 0;
+        const double keep = hi ? B : A;
+        const double send = hi ? A : B;
+        return keep + partner_d<M>(send);
+    }
+    template <int M>
+    __device__ __forceinline__ double both(double A) const { return A + partner_d<M>(A); }
+};
 
 // block_reduce_store for split sums: the state after the reduce-scatter's first (lane bit 32) step of block_reduce_store,
-// which the per-pair exchange already did; the remaining steps, then value -> term.
+// which the per-pair exchange already did; the remaining steps over the 22 values alone (rs22_reduce: 23 exchanges; with
+// the values padded to 32 slots they were 31, ten of them trading zeros), then lane -> term.  Every lane stores its
+// total at red[wave][lane]; the threads of wave 0 that report a value (rs22_reports) sum the waves in index order and
+// store to the term's row, so that only one wave works out the lane -> value -> term mapping, behind its LDS reads.
+constexpr int kRedStride = 64;  // doubles per wave of the LDS scratch `red`
 template <int NW = kBlock / 64>
-__device__ __forceinline__ void block_reduce_store_split(double (&acc)[kSplitAcc], double* red /*LDS [NW][kNumAcc]*/, double* out,
+__device__ __forceinline__ void block_reduce_store_split(double (&acc)[kSplitAcc], double* red /*LDS [NW][kRedStride]*/, double* out,
                                                          int stride) {
+    static_assert(kSplitAcc == kRsValues, "rs22_reduce is written for the 22 split sums");
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    double a[32];
-#pragma unroll
-    for (int v = 0; v < 32; ++v) a[v] = v < kSplitAcc ? acc[v] : 0.0;
-    rs_step<16>(a, lane);
-    rs_step<8>(a, lane);
-    rs_step<4>(a, lane);
-    rs_step<2>(a, lane);
-    rs_step<1>(a, lane);
-    // lane l holds the wave sum of value l: low value l (l < 32) or high value l - 32
-    const int k = lane & 31;
-    if (k < kSplitAcc) red[w * kNumAcc + (lane < 32 ? split_lo_term(k) : split_hi_term(k))] = a[0];
+    const double total = rs22_reduce(RsLaneOps{lane}, acc);
+    red[w * kRedStride + lane] = total;
     lds_barrier();
-    if ((int)threadIdx.x < kNumAcc) {
-        const int v = threadIdx.x;
-        double s = red[v];
+    if (w == 0 && rs22_reports(lane & 31)) {
+        // low value k (lanes 0-31) or high value k (lanes 32-63) -> index of the 44 reduced values
+        const int k = rs22_value(lane & 31);
+        const int v = split_term(lane >= 32, k);
+        double s = red[lane];
 #pragma unroll
-        for (int q = 1; q < NW; ++q) s += red[q * kNumAcc + v];
+        for (int q = 1; q < NW; ++q) s += red[q * kRedStride + lane];
+        // write-through (sc1) store: visible at agent scope once drained, no L2 write-back fence needed
         __hip_atomic_store(out + (size_t)v * stride, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
