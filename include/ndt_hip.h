@@ -26,7 +26,9 @@ extern "C" {
  * ndt_sc_result; no earlier layout changed); 4 = the pose-graph surface (ndt_pgo_params, ndt_pgo_result, ndt_pgo_record;
  * no earlier layout changed); 5 = the ISC surface (ndt_isc_params, ndt_isc_result); no earlier layout changed; 6 =
  * ndt_pass_geometry (its 8 ints); no earlier layout changed; ground surface added at 6, size-checked (ndt_ground_params and
- * ndt_ground_result start with their own size, which the library checks; no earlier layout changed).  A caller built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
+ * ndt_ground_result start with their own size, which the library checks; no earlier layout changed); position factors of
+ * the pose graph added at 6 (ndt_pgo_add_position, ndt_pgo_get_position_weights: two functions, no struct or buffer layout
+ * of their own; no earlier layout changed).  A caller built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
 #define NDT_HIP_ABI_VERSION 6
 
 typedef struct ndt_ctx ndt_ctx;
@@ -439,7 +441,9 @@ ndt_status ndt_isc_get(ndt_isc* isc, int index, unsigned char* bytes, double* po
  * (DESIGN.md "Pose graph", parity unpinned): one SE(3) pose per keyframe in f64, tangent order [wx wy wz vx vy vz],
  * retraction X <- X Exp(d); a prior on node 0 with residual Log(P^-1 X0); between factors with residual
  * e = Log(Z^-1 Xi^-1 Xj) (the full SE(3) logarithm, GTSAM's GTSAM_POSE3_EXPMAP chart) whitened by 1/sqrt(var), and an
- * optional Cauchy kernel (weight k^2 / (k^2 + |e|^2_S), cost k^2/2 log(1 + |e|^2_S / k^2); k = 0: Gaussian).  The result
+ * optional Cauchy kernel (weight k^2 / (k^2 + |e|^2_S), cost k^2/2 log(1 + |e|^2_S / k^2); k = 0: Gaussian); position
+ * factors (pgo_node's gtsam::GPSFactor under useGPS, :103-111, :278-287) with residual t_k - z, the translation of X_k less
+ * the measured point, whitened and weighted the same way, Jacobian [0 R_k].  The result
  * is a stationary point of the total robust cost, reached by iteratively reweighted Gauss-Newton with exact Jacobians;
  * iSAM2's estimate differs from it by its relinearisation threshold and the order in which loops arrive.
  * Poses and measurements are column-major 4 x 4 doubles (as final_tf is) and must be finite rigid transforms.
@@ -481,7 +485,11 @@ ndt_status ndt_pgo_add_node(ndt_pgo* pgo, const double pose[16], int* index);
 /* BetweenFactor(i, j, Z) with diagonal variances and a Cauchy kernel of width robust_k (0: none).  i != j, both stored
  * nodes, either order. */
 ndt_status ndt_pgo_add_between(ndt_pgo* pgo, int i, int j, const double Z[16], const double var[6], double robust_k);
-/* One optimisation, from the current estimate (a call after more nodes or edges is a warm start, as ISAM2Update is); one
+/* GPSFactor(node, xyz) with diagonal variances and a Cauchy kernel of width robust_k (0: none).  xyz is in metres in the
+ * map frame (pgo_node.cpp:278-287 gives the keyframe's own x and y with variance 1e9 and the altitude less the first fix's
+ * with variance 250).  A stored node, finite xyz, finite positive variances; a node may carry any number of them. */
+ndt_status ndt_pgo_add_position(ndt_pgo* pgo, int node, const double xyz[3], const double var[3], double robust_k);
+/* One optimisation, from the current estimate (a call after more nodes or factors is a warm start, as ISAM2Update is); one
  * launch, synchronises.  A residual rotation within 1e-6 of pi is NDT_EINVAL and a non-finite cost or step NDT_EOVERFLOW;
  * the estimate is then left as it was. */
 ndt_status ndt_pgo_optimize(ndt_pgo* pgo, ndt_pgo_result* out);
@@ -489,6 +497,8 @@ ndt_status ndt_pgo_optimize(ndt_pgo* pgo, ndt_pgo_result* out);
 ndt_status ndt_pgo_get_poses(ndt_pgo* pgo, double* poses16, int cap, int* n_out);
 /* The robust weight of every between factor the last optimise held, at its returned estimate, in insertion order. */
 ndt_status ndt_pgo_get_weights(ndt_pgo* pgo, double* w, int cap, int* n_out);
+/* The robust weight of every position factor the last optimise held, in insertion order. */
+ndt_status ndt_pgo_get_position_weights(ndt_pgo* pgo, double* w, int cap, int* n_out);
 /* One record per step of the last optimise. */
 ndt_status ndt_pgo_history(ndt_pgo* pgo, ndt_pgo_record* out, int cap, int* n_out);
 

@@ -4,6 +4,7 @@
     rocprofv3 --kernel-trace -d DIR -o run --output-format csv -- python tools/pgo_profile.py   # the workload, traced
     python tools/pgo_profile.py --summarise DIR/run_kernel_trace.csv                             # kernel times
     python tools/pgo_profile.py --restatement                                                    # tests/pgo_restate.py, no GPU
+    python tools/pgo_profile.py --altitude                          # the workload with a position factor on every keyframe
 
 The graph: 1541 keyframes (the reference run's keyframe count) taken evenly from the KITTI-00 ground-truth trajectory
 (tests/golden/kitti00_gt.npz), odometry drifted by a seeded tangent noise of 1e-3 rad / 1e-2 m per step (one sigma of
@@ -13,6 +14,8 @@ older, measured from the truth with 0.02 tangent noise and variance 0.1 (an ICP 
 The workload optimises the same graph WARMUP + REPEATS times (each from the drifted input) and prints one JSON line with
 the host wall time of the call and the optimiser's own record; --summarise reads k_pgo_optimize's dispatches out of the
 trace.  --restatement times tests/pgo_restate.py (sparse normal equations) on the same graph, for scale.
+--altitude (profiles/posegraph_gps.md) adds pgo_node's GPS factor to every keyframe: its own x and y with variance 1e9,
+the true altitude with variance 250, Cauchy k = 1.
 """
 import argparse
 import csv
@@ -71,7 +74,7 @@ def rms(A, B):
     return float(np.sqrt(((A - B)[:, :3, 3] ** 2).sum(1).mean()))
 
 
-def device():
+def device(altitude=False):
     import xchu_slam_amd as xa
     true, est, loops = graph()
     wall, info, hist, X = [], None, None, None
@@ -81,12 +84,16 @@ def device():
                 pg.add_node(P)
             for i, j, Z, var, k in loops:
                 pg.add_loop(i, j, Z, var, k)
+            if altitude:
+                for k in range(len(est)):
+                    pg.add_position(k, [est[k, 0, 3], est[k, 1, 3], true[k, 2, 3]], [1e9, 1e9, 250.0], 1.0)
             t0 = time.perf_counter()
             info = pg.optimize()
             wall.append((time.perf_counter() - t0) * 1e3)
             hist, X = pg.history(), pg.poses()
-    print(json.dumps({"nodes": len(est), "loops": len(loops), "ms_wall_call": float(statistics.median(wall[WARMUP:])), "info": info,
-                      "cg_per_iteration": [r["cg_iterations"] for r in hist], "rms_in_m": rms(est, true), "rms_out_m": rms(X, true)}))
+    print(json.dumps({"nodes": len(est), "loops": len(loops), "positions": len(est) if altitude else 0, "ms_wall_call": float(statistics.median(wall[WARMUP:])), "info": info,
+                      "cg_per_iteration": [r["cg_iterations"] for r in hist], "rms_in_m": rms(est, true), "rms_out_m": rms(X, true),
+                      "z_rms_in_m": float(np.sqrt(((est - true)[:, 2, 3] ** 2).mean())), "z_rms_out_m": float(np.sqrt(((X - true)[:, 2, 3] ** 2).mean()))}))
 
 
 def summarise(path):
@@ -111,6 +118,7 @@ def restatement():
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--restatement", action="store_true")
+    ap.add_argument("--altitude", action="store_true")
     ap.add_argument("--summarise", metavar="KERNEL_TRACE_CSV", default="")
     a = ap.parse_args()
     if a.summarise:
@@ -118,4 +126,4 @@ if __name__ == "__main__":
     elif a.restatement:
         restatement()
     else:
-        device()
+        device(a.altitude)

@@ -8,7 +8,7 @@ from .icp import IterativeClosestPoint, refine_loop  # noqa: F401
 from .gicp import GeneralizedIterativeClosestPoint  # noqa: F401
 from .scancontext import SCManager, close_loops, detect_loops  # noqa: F401
 from .isc import ISCGeneration, detect_loops_isc  # noqa: F401
-from .posegraph import PoseGraph, loop_measurement, optimize_loops  # noqa: F401
+from .posegraph import PoseGraph, gps_factors, loop_measurement, optimize_loops  # noqa: F401
 from .globalmap import KeyframeMap, read_g2o, read_pcd, save_map, write_g2o, write_pcd, write_tum  # noqa: F401
 from .ground import CloudFilter, GroundResult, detect_ground  # noqa: F401
 from .ndt import (DIRECT1, DIRECT7, DIRECT26, KDTREE, CpuNormalDistributionsTransform, NormalDistributionsTransform,  # noqa: F401

@@ -401,9 +401,11 @@ SIGNATURES = {
     "ndt_pgo_size": (C.c_int, [_P]),
     "ndt_pgo_add_node": (C.c_int, [_P, _DP, C.POINTER(C.c_int)]),
     "ndt_pgo_add_between": (C.c_int, [_P, C.c_int, C.c_int, _DP, _DP, C.c_double]),
+    "ndt_pgo_add_position": (C.c_int, [_P, C.c_int, _DP, _DP, C.c_double]),
     "ndt_pgo_optimize": (C.c_int, [_P, C.POINTER(PgoResult)]),
     "ndt_pgo_get_poses": (C.c_int, [_P, _DP, C.c_int, C.POINTER(C.c_int)]),
     "ndt_pgo_get_weights": (C.c_int, [_P, _DP, C.c_int, C.POINTER(C.c_int)]),
+    "ndt_pgo_get_position_weights": (C.c_int, [_P, _DP, C.c_int, C.POINTER(C.c_int)]),
     "ndt_pgo_history": (C.c_int, [_P, C.POINTER(PgoRecord), C.c_int, C.POINTER(C.c_int)]),
     "ndt_map_create": (C.c_int, [_P, C.POINTER(_P)]),
     "ndt_map_destroy": (None, [_P]),

@@ -10,12 +10,15 @@ struct ndt_pgo {
     std::vector<double> given_last;         // the last node's pose as given (the next odometry edge starts from it)
     std::vector<int> li, lj;
     std::vector<double> Zl, lvar, lk;
+    std::vector<int> pnode;                 // position factors: the node; [7] measured xyz, variances, robust k
+    std::vector<double> pf;
     DevBuf<double> d_f64;
     DevBuf<int> d_i32;
     DevBuf<ndt_pgo_record> d_hist;
     DevBuf<PgoOut> d_out;
     std::vector<ndt_pgo_record> hist;       // of the last optimise
-    std::vector<double> weights;            // of the last optimise
+    std::vector<double> weights;            // of the last optimise (between factors)
+    std::vector<double> pweights;           // of the last optimise (position factors)
 };
 
 // column-major 4 x 4 -> R row-major, t; false when it is not a finite rigid transform
@@ -120,16 +123,33 @@ ndt_status ndt_pgo_add_between(ndt_pgo* g, int i, int j, const double Z[16], con
     return NDT_OK;
 }
 
+ndt_status ndt_pgo_add_position(ndt_pgo* g, int node, const double xyz[3], const double var[3], double robust_k) {
+    if (!g) return NDT_EINVAL;
+    ndt_ctx* c = g->c;
+    if (!xyz || !var) return fail(c, NDT_EINVAL, "null argument");
+    if (node < 0 || node >= ndt_pgo_size(g)) return fail(c, NDT_EINVAL, "position factor: node index out of range");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(xyz[a])) return fail(c, NDT_EINVAL, "position factor: position is not finite");
+    for (int a = 0; a < 3; ++a)
+        if (!(var[a] > 0.0) || !std::isfinite(var[a])) return fail(c, NDT_EINVAL, "position factor: variances must be positive and finite");
+    if (!(robust_k >= 0.0) || !std::isfinite(robust_k)) return fail(c, NDT_EINVAL, "position factor: robust k must be >= 0");
+    g->pnode.push_back(node);
+    g->pf.insert(g->pf.end(), xyz, xyz + 3);
+    g->pf.insert(g->pf.end(), var, var + 3);
+    g->pf.push_back(robust_k);
+    return NDT_OK;
+}
+
 ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
     if (!g) return NDT_EINVAL;
     ndt_ctx* c = g->c;
     if (!out) return fail(c, NDT_EINVAL, "null argument");
-    const size_t n = (size_t)ndt_pgo_size(g), m = g->li.size();
+    const size_t n = (size_t)ndt_pgo_size(g), m = g->li.size(), np = g->pnode.size();
     if (n == 0) return fail(c, NDT_EINVAL, "the pose graph has no node");
-    if (m > 0x3fffffffULL / 36 || n > 0x3fffffffULL / 18) return fail(c, NDT_EINVAL, "pose graph too large");
+    if (m > 0x3fffffffULL / 36 || n > 0x3fffffffULL / 18 || np > 0x3fffffffULL / 14) return fail(c, NDT_EINVAL, "pose graph too large");
     TRY(set_dev(c));
-    // per-node lists of loop edges (2 * edge + side), edges in insertion order
-    std::vector<int> ints(2 * m + n + 1 + 2 * m, 0);
+    // per-node lists of loop edges (2 * edge + side), edges in insertion order; the position factors' slots by node
+    std::vector<int> ints(2 * m + n + 1 + 2 * m + n + 1 + np, 0);
     int* h_li = ints.data();
     int* h_lj = h_li + m;
     int* h_off = h_lj + m;
@@ -148,9 +168,21 @@ ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
             h_ent[fill[g->lj[q]]++] = (int)(2 * q + 1);
         }
     }
-    // inputs, contiguous: X, Zc, Zl, lvar, lk; then the work arrays
-    const size_t n_in = 24 * n + 19 * m;
-    const size_t n_f64 = n_in + 12 * n + 18 * n + 6 * n * 7 + 36 * m + 6 * m * 2 + m;
+    int* h_poff = h_ent + 2 * m;
+    int* h_pnode = h_poff + n + 1;
+    std::vector<int> slot(np);  // of each position factor: by node, a node's in insertion order
+    for (size_t q = 0; q < np; ++q) ++h_poff[g->pnode[q] + 1];
+    for (size_t k = 0; k < n; ++k) h_poff[k + 1] += h_poff[k];
+    {
+        std::vector<int> fill(h_poff, h_poff + n);
+        for (size_t q = 0; q < np; ++q) {
+            slot[q] = fill[g->pnode[q]]++;
+            h_pnode[slot[q]] = g->pnode[q];
+        }
+    }
+    // inputs, contiguous: X, Zc, Zl, lvar, lk, the position factors by slot; then the work arrays
+    const size_t n_in = 24 * n + 19 * m + 7 * np;
+    const size_t n_f64 = n_in + 12 * n + 18 * n + 6 * n * 7 + 36 * m + 6 * m * 2 + m + 7 * np;
     std::vector<double> in;
     in.reserve(n_in);
     in.insert(in.end(), g->X.begin(), g->X.end());
@@ -158,6 +190,8 @@ ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
     in.insert(in.end(), g->Zl.begin(), g->Zl.end());
     in.insert(in.end(), g->lvar.begin(), g->lvar.end());
     in.insert(in.end(), g->lk.begin(), g->lk.end());
+    in.resize(n_in);
+    for (size_t q = 0; q < np; ++q) std::copy_n(g->pf.data() + 7 * q, 7, in.data() + n_in - 7 * np + 7 * (size_t)slot[q]);
     TRY(ensure(c, g->d_f64, n_f64));
     TRY(ensure(c, g->d_i32, ints.size()));
     TRY(ensure(c, g->d_hist, (size_t)g->prm.max_iter + 1));
@@ -168,6 +202,7 @@ ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
     PgoGraph d;
     d.n = (int)n;
     d.m = (int)m;
+    d.np = (int)np;
     double* f = g->d_f64.p;
     auto take = [&f](size_t count) {
         double* p = f;
@@ -179,6 +214,8 @@ ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
     d.Zl = take(12 * m);
     d.lvar = take(6 * m);
     d.lk = take(m);
+    d.pf = take(7 * np);
+    double* const d_pwork = take(7 * np);
     d.Xprev = take(12 * n);
     d.Jc = take(18 * n);
     d.rc = take(6 * n);
@@ -196,6 +233,7 @@ ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
     d.lj = d.li + m;
     d.off = d.lj + m;
     d.ent = d.off + n + 1;
+    d.poff = d.ent + 2 * m;
     d.hist = g->d_hist.p;
     d.out = g->d_out.p;
     PgoArgs a;
@@ -220,8 +258,14 @@ ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
     if (o.status != kPgoOk) return fail(c, NDT_EOVERFLOW, "the optimisation left the finite range; the estimate is unchanged");
     g->hist.resize((size_t)o.iterations);
     g->weights.resize(m);
+    g->pweights.resize(np);
     HIPCHK(c, hipMemcpy(g->X.data(), d.X, 12 * n * sizeof(double), hipMemcpyDeviceToHost));
     if (m) HIPCHK(c, hipMemcpy(g->weights.data(), d.w, m * sizeof(double), hipMemcpyDeviceToHost));
+    if (np) {
+        std::vector<double> work(7 * np);
+        HIPCHK(c, hipMemcpy(work.data(), d_pwork, 7 * np * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t q = 0; q < np; ++q) g->pweights[q] = work[7 * (size_t)slot[q] + 6];
+    }
     if (o.iterations) HIPCHK(c, hipMemcpy(g->hist.data(), d.hist, (size_t)o.iterations * sizeof(ndt_pgo_record), hipMemcpyDeviceToHost));
     out->iterations = o.iterations;
     out->converged = o.converged;
@@ -256,6 +300,15 @@ ndt_status ndt_pgo_get_weights(ndt_pgo* g, double* w, int cap, int* n_out) {
     if (n_out) *n_out = n;
     if (cap < 0 || (cap && !w)) return fail(g->c, NDT_EINVAL, "bad output arguments");
     std::copy(g->weights.begin(), g->weights.begin() + std::min(n, cap), w);
+    return NDT_OK;
+}
+
+ndt_status ndt_pgo_get_position_weights(ndt_pgo* g, double* w, int cap, int* n_out) {
+    if (!g) return NDT_EINVAL;
+    const int n = (int)g->pweights.size();
+    if (n_out) *n_out = n;
+    if (cap < 0 || (cap && !w)) return fail(g->c, NDT_EINVAL, "bad output arguments");
+    std::copy(g->pweights.begin(), g->pweights.begin() + std::min(n, cap), w);
     return NDT_OK;
 }
 

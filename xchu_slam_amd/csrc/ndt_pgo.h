@@ -32,9 +32,12 @@ struct PgoOut {
 
 // One graph on the device.  Chain factor k is the prior (k == 0, measurement = the first pose as given) or the odometry
 // edge (k - 1, k); loop edges are the ndt_pgo_add_between ones.  ent[off[k] .. off[k + 1]) lists node k's loop edges as
-// 2 * edge + side (side 1: the node is the edge's j).
+// 2 * edge + side (side 1: the node is the edge's j).  Position factors are the ndt_pgo_add_position ones (residual
+// t_k - z, no logarithm), stored by node and within a node in insertion order (the host sorts them and puts the weights
+// back in insertion order): node k's are the slots poff[k] .. poff[k + 1].  They share two pointers, not one per array:
+// the kernel already runs out of registers.
 struct PgoGraph {
-    int n, m;
+    int n, m, np;
     double* X;            // [n][12] the estimate
     double* Xprev;        // [n][12] the estimate before the last step
     const double* Zc;     // [n][12]
@@ -51,6 +54,8 @@ struct PgoGraph {
     double* bv;           // [m][6]  w K^T S e
     double* dl;           // [m][6]  per-edge product of the matrix-vector step
     double* w;            // [m]     robust weights
+    const int* poff;      // [n + 1], then [np] each position factor's node
+    double* pf;           // [np][7] measured xyz, variances, robust k (0: Gaussian); then [np][7] w / var, w (t_k - z) / var, w
     double* z;            // [n][6]  prefix sums (world frame)
     double* tmp;          // [n][6]  a scan's per-thread running sums
     double* y;            // [n][6]  CG iterate, residual, direction, product

@@ -10,6 +10,11 @@
 // and a loop edge's row of Al Ac^-1 is  K_e (E_j - E_i) L P  with  K_e = S Jr^-1(e) Ad(X_j^-1): in the world frame a
 // loop sees the difference of two prefix sums.  One product with I + B^T B is therefore a prefix sum, one 6 x 6 product
 // per loop edge (N_e = w K^T K), a per-node gather over the host-built edge lists, a suffix sum and P^T.
+// A position factor on node k (residual t_k - z, Jacobian [0 R_k]) sees one prefix sum: its row of Al Ac^-1 is
+// S^-1/2 K_k E_k L P with K_k = [-hat(t_k), I], so K u = u_v - t_k x u_w and K^T c = [t_k x c; c].  It adds
+// w K^T (iv . (K z_k)) to node k's gather in the product and w K^T (iv . r) in the right-hand side (iv = 1 / var), both
+// formed in the gather itself from three stored doubles; a node's between edges come first, then its position factors
+// in insertion order.
 //
 // Determinism: every sum runs in a fixed order (per-thread runs, wave shuffles, then the waves in order); there are no
 // floating-point atomics.  Nothing here waits on another workgroup, so there is no wait loop.
@@ -148,6 +153,30 @@ __device__ inline void gather_node(const PgoGraph& g, int k, const double* src, 
     }
 }
 
+// Adds node k's position factors to the gather f: w K^T (iv . (K z_k)) (OP: the matrix-vector step, after g.z is
+// complete), else w K^T (iv . r), in insertion order.  t_k is read from g.X, which does not move during CG.
+template <bool OP> __device__ inline void gather_positions(const PgoGraph& g, int k, double* f) {
+    const int lo = g.poff[k], hi = g.poff[k + 1];
+    if (lo == hi) return;
+    const double* t = g.X + 12 * (size_t)k + 9;
+    double ku[3];
+    if (OP) {
+        const double* u = g.z + 6 * (size_t)k;
+        cross3(t, u, ku);
+        for (int i = 0; i < 3; ++i) ku[i] = u[3 + i] - ku[i];
+    }
+    const double* work = g.pf + 7 * (size_t)g.np;
+    for (int q = lo; q < hi; ++q) {
+        double c[3], x[3];
+        for (int i = 0; i < 3; ++i) c[i] = OP ? work[7 * (size_t)q + i] * ku[i] : work[7 * (size_t)q + 3 + i];
+        cross3(t, c, x);
+        for (int i = 0; i < 3; ++i) {
+            f[i] = f[i] + x[i];
+            f[3 + i] = f[3 + i] + c[i];
+        }
+    }
+}
+
 // Residuals, robust weights and the linearisation at the current estimate; returns the total robust cost, or sets
 // s.bad to the lowest factor whose residual rotation is within kPgoPiMargin of pi.
 __device__ double evaluate(const PgoGraph& g, const PgoArgs& a, PgoLds& s) {
@@ -232,6 +261,31 @@ __device__ double evaluate(const PgoGraph& g, const PgoArgs& a, PgoLds& s) {
             }
         }
     }
+    for (int q = threadIdx.x; q < g.np; q += kPgoBlock) {
+        const double* t = g.X + 12 * (size_t)g.poff[g.n + 1 + q] + 9;
+        const double* in = g.pf + 7 * (size_t)q;
+        double* work = g.pf + 7 * ((size_t)g.np + q);
+        double r[3], iv[3], s2 = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            r[i] = t[i] - in[i];
+            iv[i] = 1.0 / in[3 + i];
+            s2 = s2 + r[i] * r[i] * iv[i];
+        }
+        const double rk = in[6];
+        double w = 1.0;
+        if (rk > 0.0) {
+            const double k2 = rk * rk;
+            w = k2 / (k2 + s2);
+            cost = cost + 0.5 * k2 * log1p(s2 / k2);
+        } else {
+            cost = cost + 0.5 * s2;
+        }
+        for (int i = 0; i < 3; ++i) {
+            work[i] = w * iv[i];
+            work[3 + i] = w * (iv[i] * r[i]);
+        }
+        work[6] = w;
+    }
     return block_sum(cost, s);
 }
 
@@ -260,7 +314,11 @@ __device__ double apply_h(const PgoGraph& g, const PgoArgs& a, PgoLds& s) {
     __syncthreads();
     double dot = 0.0;  // this thread's nodes, in its run's order
     scan6<true>(
-        g.n, g.tmp, s, [&](int k, double* v) { gather_node(g, k, g.dl, v); },
+        g.n, g.tmp, s,
+        [&](int k, double* v) {
+            gather_node(g, k, g.dl, v);
+            gather_positions<true>(g, k, v);
+        },
         [&](int k, const double* v, double* o) {
             apply_pt(g, a, k, v, o);
             for (int i = 0; i < 6; ++i) {
@@ -304,7 +362,11 @@ __global__ __launch_bounds__(kPgoBlock) void k_pgo_optimize(PgoGraph g, PgoArgs 
 
         // right-hand side  -rc - B^T rl  into r, p; y = 0
         scan6<true>(
-            n, g.tmp, s, [&](int k, double* v) { gather_node(g, k, g.bv, v); },
+            n, g.tmp, s,
+            [&](int k, double* v) {
+                gather_node(g, k, g.bv, v);
+                gather_positions<false>(g, k, v);
+            },
             [&](int k, const double* v, double* o) {
                 apply_pt(g, a, k, v, o);
                 for (int i = 0; i < 6; ++i) o[i] = -g.rc[6 * (size_t)k + i] - o[i];

@@ -11,7 +11,9 @@ what it asks GTSAM for, solved as a batch problem (DESIGN.md "Pose graph", parit
         info = pg.optimize()
         poses6d = pg.poses6d()
 
-`optimize_loops` does exactly that with what `close_loops` returns.
+`optimize_loops` does exactly that with what `close_loops` returns.  Under `useGPS` pgo_node also adds a
+gtsam::GPSFactor per keyframe that has a fix (pgo_node.cpp:103-111, 168-182, 207-212, 278-287): `pg.add_position(node,
+xyz, variances)`, and `gps_factors` builds those from keyframe and fix times.
 """
 from __future__ import annotations
 
@@ -25,7 +27,7 @@ from ._ctxobj import _CtxObject
 from ._lib import PgoParams, PgoRecord, PgoResult, check
 from .ndt import NormalDistributionsTransform, _dp
 
-__all__ = ["PoseGraph", "loop_measurement", "optimize_loops"]
+__all__ = ["PoseGraph", "gps_factors", "loop_measurement", "optimize_loops"]
 
 _PARAM_NAMES = tuple(k for k, _ in PgoParams._fields_)
 
@@ -89,6 +91,15 @@ class PoseGraph(_CtxObject):
         var = np.ascontiguousarray(np.broadcast_to(np.asarray(variances, np.float64), (6,)))
         check(self._lib.ndt_pgo_add_between(self._handle, int(i), int(j), _dp(_colmajor(_pose44(Z))), _dp(var), float(robust_k)), self.ctx)
 
+    def add_position(self, node: int, xyz, variances, robust_k: float = 1.0):
+        """GPSFactor(node, xyz): the node's translation measured as xyz (metres, map frame); variances is one number
+        or three (pgo_node: 1e9, 1e9, 250 - altitude only); robust_k as for add_loop."""
+        p = np.ascontiguousarray(np.asarray(xyz, np.float64).reshape(-1))
+        if p.shape != (3,):
+            raise ValueError("a position is (x, y, z)")
+        var = np.ascontiguousarray(np.broadcast_to(np.asarray(variances, np.float64), (3,)))
+        check(self._lib.ndt_pgo_add_position(self._handle, int(node), _dp(p), _dp(var), float(robust_k)), self.ctx)
+
     def optimize(self) -> dict:
         """One optimisation from the current estimate (a later call is a warm start)."""
         r = PgoResult()
@@ -117,6 +128,14 @@ class PoseGraph(_CtxObject):
         check(self._lib.ndt_pgo_get_weights(self._handle, None, 0, C.byref(n)), self.ctx)
         buf = np.empty(max(1, n.value), np.float64)
         check(self._lib.ndt_pgo_get_weights(self._handle, _dp(buf), n.value, None), self.ctx)
+        return buf[:n.value].copy()
+
+    def position_weights(self) -> np.ndarray:
+        """The final robust weight of every position factor of the last optimize(), in the order they were added."""
+        n = C.c_int()
+        check(self._lib.ndt_pgo_get_position_weights(self._handle, None, 0, C.byref(n)), self.ctx)
+        buf = np.empty(max(1, n.value), np.float64)
+        check(self._lib.ndt_pgo_get_position_weights(self._handle, _dp(buf), n.value, None), self.ctx)
         return buf[:n.value].copy()
 
     def history(self) -> list[dict]:
@@ -157,18 +176,54 @@ def loop_measurement(poses, loop_idx: int, curr_idx: int, T_icp, literal_measure
     return _inv(_pose44(poses[loop_idx])) @ T @ _pose44(poses[curr_idx])
 
 
+def gps_factors(keyframe_times, poses, gps_times, altitudes, eps: float = 0.1, altitude_var: float = 250.0, xy_var: float = 1e9):
+    """pgo_node's GPS factors for a replay (host numpy): [(node, xyz (3,), var (3,))] for add_position / optimize_loops.
+
+    The rule of pgo_node.cpp:168-182, 207-212, 278-287 stated as what it means (its queue handling returns with the mutex
+    held on a match and its own comment calls GPS not usable yet, so the intent is restated, not the code path): keyframe
+    k has GPS iff its nearest fix in time is strictly within eps seconds (an equal distance goes to the earlier fix); the
+    altitude offset is the altitude of the first keyframe that has GPS; the constraint is (x, y of that keyframe's pose,
+    altitude - offset) with variances (xy_var, xy_var, altitude_var): only the altitude is constrained.  The reference
+    takes x and y from recentOptimizedX/Y, the last optimised pose rather than this keyframe's; at a variance of 1e9 the
+    difference is far below the solver's step (modelled).  Altitudes are metres; a NavSatFix's latitude and longitude
+    are not used."""
+    kt = np.asarray(keyframe_times, np.float64).reshape(-1)
+    gt = np.asarray(gps_times, np.float64).reshape(-1)
+    alt = np.asarray(altitudes, np.float64).reshape(-1)
+    if len(poses) != len(kt) or len(gt) != len(alt):
+        raise ValueError("one time per keyframe pose and one altitude per fix")
+    out, offset = [], None
+    if len(gt) == 0:
+        return out
+    order = np.argsort(gt, kind="stable")       # argmin below then takes the earlier of two equally near fixes
+    gt, alt = gt[order], alt[order]
+    for k, t in enumerate(kt):
+        f = int(np.argmin(np.abs(gt - t)))
+        if not abs(gt[f] - t) < eps:
+            continue
+        if offset is None:
+            offset = alt[f]
+        P = _pose44(poses[k])
+        out.append((k, np.array([P[0, 3], P[1, 3], alt[f] - offset]), np.array([xy_var, xy_var, altitude_var], np.float64)))
+    return out
+
+
 def optimize_loops(poses, accepted, literal_measurement: bool = False, robust_k: float = 1.0, device: int = 0, registration=None,
-                   **params):
+                   positions=None, **params):
     """pgo_node's back end for a replay: the graph of `poses` (per keyframe a 4 x 4 or (x, y, z, roll, pitch, yaw)) and
     of `accepted` as close_loops returns it ([(loop_idx, curr_idx, transform, score)]; the score is the loop factor's
-    variance, as pgo_node.cpp:453-457 has it), one optimise.  Returns (poses6d (n, 6), info); info is optimize()'s dict
-    plus "weights" and "poses" (n, 4, 4)."""
+    variance, as pgo_node.cpp:453-457 has it) and of `positions` ([(node, xyz, var)] as gps_factors returns it, each a
+    position factor with robust_k), one optimise.  Returns (poses6d (n, 6), info); info is optimize()'s dict plus
+    "weights", "position_weights" and "poses" (n, 4, 4)."""
     with PoseGraph(device, registration, **params) as pg:
         for p in poses:
             pg.add_node(p)
         for loop_idx, curr_idx, T, score in accepted:
             pg.add_loop(loop_idx, curr_idx, loop_measurement(poses, loop_idx, curr_idx, T, literal_measurement), score, robust_k)
+        for node, xyz, var in positions or ():
+            pg.add_position(node, xyz, var, robust_k)
         info = pg.optimize()
         info["weights"] = pg.weights()
+        info["position_weights"] = pg.position_weights()
         info["poses"] = pg.poses()
         return pg.poses6d(), info
