@@ -28,7 +28,7 @@ extern "C" {
  * ndt_pass_geometry (its 8 ints); no earlier layout changed; ground surface added at 6, size-checked (ndt_ground_params and
  * ndt_ground_result start with their own size, which the library checks; no earlier layout changed); position factors of
  * the pose graph added at 6 (ndt_pgo_add_position, ndt_pgo_get_position_weights: two functions, no struct or buffer layout
- * of their own; no earlier layout changed).  A caller built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
+ * of their own; no earlier layout changed); ndt_pgo_set_estimate added at 6 (one function, no layout of its own).  A caller built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
 #define NDT_HIP_ABI_VERSION 6
 
 typedef struct ndt_ctx ndt_ctx;
@@ -482,6 +482,11 @@ int ndt_pgo_size(const ndt_pgo* pgo);
 /* A keyframe pose.  Node 0 gets the prior (mean = this pose); every later node gets the odometry edge from its
  * predecessor, measured between the two poses as given (Run(), :249-291).  The pose is also the node's initial estimate. */
 ndt_status ndt_pgo_add_node(ndt_pgo* pgo, const double pose[16], int* index);
+/* The estimate of a stored node replaced by `pose` (a finite rigid transform, as add_node's).  Host state only: no factor
+ * changes and nothing is launched.  For a caller that appends a node whose only new factor is its odometry edge to an
+ * optimised graph: the estimate X_{k-1} (P_{k-1}^-1 P_k) makes that edge's residual zero, so a stationary estimate stays
+ * stationary and no optimise is needed. */
+ndt_status ndt_pgo_set_estimate(ndt_pgo* pgo, int node, const double pose[16]);
 /* BetweenFactor(i, j, Z) with diagonal variances and a Cauchy kernel of width robust_k (0: none).  i != j, both stored
  * nodes, either order. */
 ndt_status ndt_pgo_add_between(ndt_pgo* pgo, int i, int j, const double Z[16], const double var[6], double robust_k);

@@ -400,6 +400,7 @@ SIGNATURES = {
     "ndt_pgo_destroy": (None, [_P]),
     "ndt_pgo_size": (C.c_int, [_P]),
     "ndt_pgo_add_node": (C.c_int, [_P, _DP, C.POINTER(C.c_int)]),
+    "ndt_pgo_set_estimate": (C.c_int, [_P, C.c_int, _DP]),
     "ndt_pgo_add_between": (C.c_int, [_P, C.c_int, C.c_int, _DP, _DP, C.c_double]),
     "ndt_pgo_add_position": (C.c_int, [_P, C.c_int, _DP, _DP, C.c_double]),
     "ndt_pgo_optimize": (C.c_int, [_P, C.POINTER(PgoResult)]),

@@ -103,6 +103,17 @@ ndt_status ndt_pgo_add_node(ndt_pgo* g, const double pose[16], int* index) {
     return NDT_OK;
 }
 
+// Host state only: the estimate of one node.  The factors keep the poses they were built from (Zc, given_last).
+ndt_status ndt_pgo_set_estimate(ndt_pgo* g, int node, const double pose[16]) {
+    if (!g) return NDT_EINVAL;
+    if (!pose) return fail(g->c, NDT_EINVAL, "null argument");
+    if (node < 0 || node >= ndt_pgo_size(g)) return fail(g->c, NDT_EINVAL, "set estimate: node index out of range");
+    double P[12];
+    if (!pgo_read_pose(pose, P)) return fail(g->c, NDT_EINVAL, "pose is not a finite rigid transform");
+    std::copy(P, P + 12, g->X.begin() + 12 * (size_t)node);
+    return NDT_OK;
+}
+
 ndt_status ndt_pgo_add_between(ndt_pgo* g, int i, int j, const double Z[16], const double var[6], double robust_k) {
     if (!g) return NDT_EINVAL;
     ndt_ctx* c = g->c;

@@ -85,6 +85,10 @@ class PoseGraph(_CtxObject):
         check(self._lib.ndt_pgo_add_node(self._handle, _dp(_colmajor(_pose44(pose))), C.byref(idx)), self.ctx)
         return idx.value
 
+    def set_estimate(self, node: int, pose):
+        """The estimate of a stored node replaced by `pose` (as add_node takes it); host state only, no factor changes."""
+        check(self._lib.ndt_pgo_set_estimate(self._handle, int(node), _dp(_colmajor(_pose44(pose)))), self.ctx)
+
     def add_loop(self, i: int, j: int, Z, variances, robust_k: float = 1.0):
         """BetweenFactor(i, j, Z): variances is one number (pgo_node uses the ICP fitness score for all six) or six;
         robust_k the Cauchy kernel's width (pgo_node: 1; 0: Gaussian)."""
@@ -117,10 +121,7 @@ class PoseGraph(_CtxObject):
     def poses6d(self) -> np.ndarray:
         """(n, 6) x, y, z, roll, pitch, yaw with the angles as GTSAM's Rot3::rpy gives them, which is what
         keyframePosesUpdated receives (pgo_node.cpp:517-526)."""
-        T = self.poses()
-        R = T[:, :3, :3]
-        return np.stack([T[:, 0, 3], T[:, 1, 3], T[:, 2, 3], np.arctan2(R[:, 2, 1], R[:, 2, 2]),
-                         np.arctan2(-R[:, 2, 0], np.hypot(R[:, 2, 1], R[:, 2, 2])), np.arctan2(R[:, 1, 0], R[:, 0, 0])], -1)
+        return _poses6d(self.poses())
 
     def weights(self) -> np.ndarray:
         """The final robust weight of every loop factor of the last optimize(), in the order they were added."""
@@ -146,6 +147,13 @@ class PoseGraph(_CtxObject):
         check(self._lib.ndt_pgo_history(self._handle, buf, n.value, None), self.ctx)
         return [{"cost": float(buf[i].cost), "max_step": float(buf[i].max_step), "cg_iterations": int(buf[i].cg_iterations)}
                 for i in range(n.value)]
+
+
+def _poses6d(T: np.ndarray) -> np.ndarray:
+    """(n, 4, 4) -> (n, 6) x, y, z and GTSAM's Rot3::rpy."""
+    R = T[:, :3, :3]
+    return np.stack([T[:, 0, 3], T[:, 1, 3], T[:, 2, 3], np.arctan2(R[:, 2, 1], R[:, 2, 2]),
+                     np.arctan2(-R[:, 2, 0], np.hypot(R[:, 2, 1], R[:, 2, 2])), np.arctan2(R[:, 1, 0], R[:, 0, 0])], -1)
 
 
 def _matrix_to_pose6d(T: np.ndarray):
