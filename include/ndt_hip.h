@@ -752,10 +752,11 @@ ndt_status ndt_memcpy_d2h(ndt_ctx* ctx, void* h_dst, const void* d_src, size_t b
 /* Waits for the ctx stream and its side streams (getFitnessScore, keyframe insertion). */
 ndt_status ndt_synchronize(ndt_ctx* ctx);
 
-/* Timing of the last set_target / align on the device (HIP events, ms) and the dominant kernel's
- * average duration (derivative pass, ms) with its algorithmic bytes per launch. */
+/* Timing of the last set_target / align on the device (the 100 MHz device clock, s_memrealtime; ms) and the dominant
+ * kernel's average duration (derivative pass, ms) with its algorithmic bytes per launch. */
 ndt_status ndt_last_timings(ndt_ctx* ctx, double* ms_build, double* ms_align, double* ms_pass_avg, double* pass_bytes_avg);
-/* Profiling breakdown of the average derivative pass (ms), from in-kernel stamps: [0] workgroup bodies
+/* Profiling breakdown of the average derivative pass (ms), from in-kernel stamps; the 22 columns are named, in order, by
+ * kPhaseNames of csrc/ndt_stamps.h, which also holds the stamp slots and the phase sequences: [0] workgroup bodies
  * (first start .. last workgroup's partials stored), [1] hand-off (ticket + acquire), [2] last workgroup's
  * fixed-order partials reduction, [3] AlignState staged into LDS, [4] Newton/More-Thuente control step,
  * [5] next transform + angle tables, [6] state write-back and drain; [7..11] (profiling build

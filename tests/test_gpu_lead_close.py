@@ -217,3 +217,27 @@ def test_flagged_build_is_reported_and_rerun():
     assert ref.build_stats()["rerun"] == 0
     ref.close()
     f.close()
+
+
+@pytest.mark.parametrize("lead", [False, True])
+def test_pass_phases_by_chain_kind(pair, lead):
+    """What ndt_pass_phases reports of the product library, through the public API: a last-workgroup-tail chain stamps all
+    eight slots of a pass row, so all seven phases are > 0; a leading-tail chain's kernel stamps a pass's start and end only
+    (k_pass_lead hands tail_control no stamp pointer), so the passes are timed and every phase is 0.  Profiling changes
+    nothing of the result."""
+    g = _ctx(pair, lead)
+    g.align(pair.guess, want_output=False)
+    plain = _record(g)
+    g.close()
+    g = _ctx(pair, lead, profiling=True)
+    g.align(pair.guess, want_output=False)
+    rec, tm = _record(g), g.timings()
+    g.close()
+    _same(rec, plain, f"lead={lead} profiling on against off")
+    assert tm["ms_pass_avg"] > 0.0, tm
+    phases = tm["pass_phases_ms"]
+    assert len(phases) == 7
+    if lead:
+        assert all(v == 0.0 for v in phases.values()), phases
+    else:
+        assert all(v > 0.0 for v in phases.values()), phases

@@ -6,6 +6,8 @@
   CU counts, searches, pass options and source sizes around every threshold (tests/native/pass_geom_check.cpp).
 * the host steps every unit shares (csrc/ndt_geom.h): the strided-cloud packer, the xyzi layout rule and grid_for, also
   under the host sanitizers (tests/native/cloud_pack_check.cpp).
+* the profiling stamps' decoder (csrc/ndt_stamps.h) on synthetic stamp tables, also under the host sanitizers
+  (tests/native/stamp_decode_check.cpp).
 """
 import os
 import shutil
@@ -110,6 +112,26 @@ def test_cloud_pack_and_grid_for(tmp_path):
     src = os.path.join(HERE, "native", "cloud_pack_check.cpp")
     for tag, flags in (("plain", ["-O2"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
         exe = tmp_path / ("cpc_" + tag)
+        subprocess.run(["g++", "-std=c++17", *flags, "-o", str(exe), src], check=True)
+        out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, tag + "\n" + out.stdout + out.stderr
+        assert "mismatched: 0" in out.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_stamp_decoder(tmp_path):
+    """accumulate_pass_stats (csrc/ndt_stamps.h: what ndt_last_timings / ndt_pass_phases report) on synthetic tables of at
+    most 4 passes x 4 workgroups whose phases each last their own number of ticks, tests/native/stamp_decode_check.cpp:
+    the seven product phases, the time and the 16 N + 36 pairs bytes of one pass; rows never stamped or ending before
+    they start; a leading-tail row (timed, no phases); workgroup means with a workgroup past the scan's points and a
+    pass dropped for a row out of order; the last-workgroup tail's eight phases and the speculative-solve pair, with one
+    stamp out of order; the leading-tail kernel's tail from pass k's prologue row and pass k - 1's tail row (none for
+    k = 0); a second round accumulating into the first; passes past the table and more workgroups than rows.  Built and
+    run a second time with -fsanitize=address,undefined (a stand-alone host program: the tables are exactly as large as
+    their shape says)."""
+    src = os.path.join(HERE, "native", "stamp_decode_check.cpp")
+    for tag, flags in (("plain", ["-O2"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
+        exe = tmp_path / ("sdc_" + tag)
         subprocess.run(["g++", "-std=c++17", *flags, "-o", str(exe), src], check=True)
         out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
         assert out.returncode == 0, tag + "\n" + out.stdout + out.stderr

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Instruction identity of the library's gfx950 kernels between a base commit and the working tree:
-   tools/isa_identity.py [--base REV] [--keep DIR] [unit.hip ...]      (default: HEAD, every .hip unit of the Makefile)
+   tools/isa_identity.py [--base REV] [--keep DIR] [--define FLAG ...] [unit.hip ...]
+                                                                       (default: HEAD, every .hip unit of the Makefile)
 
 Each unit is compiled device-only from both trees with the Makefile's flags (derivatives.hip with -fno-slp-vectorize),
 disassembled with llvm-objdump -d, and compared kernel by kernel: the instruction text and encodings (addresses
 dropped, so that a kernel does not differ because an earlier one changed length), and the register / scratch / LDS
-figures of the code object's notes.  A refactor's claim that the shipped kernels do not change is this tool printing
+figures of the code object's notes.  --define FLAG (repeatable, e.g. --define=-DNDT_BODY_STAMPS) is passed to both builds,
+so that a build variant can be compared as well.  A refactor's claim that the shipped kernels do not change is this tool printing
 'identical' for every kernel.  Exit status 1 if any kernel differs."""
 import argparse
 import os
@@ -29,8 +31,8 @@ def units_of(tree):
     return re.search(r'^SRCS := (.*)$', mk, re.M).group(1).split()
 
 
-def build(tree, unit, out):
-    flags = FLAGS + (['-fno-slp-vectorize'] if unit == 'derivatives.hip' else [])
+def build(tree, unit, out, defines):
+    flags = FLAGS + defines + (['-fno-slp-vectorize'] if unit == 'derivatives.hip' else [])
     subprocess.run([HIPCC] + flags + ['-c', unit, '-o', out], cwd=os.path.join(tree, CSRC), check=True)
 
 
@@ -70,6 +72,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--base', default='HEAD')
     ap.add_argument('--keep', help='directory that keeps the code objects (default: a temporary one)')
+    ap.add_argument('--define', action='append', default=[], metavar='FLAG', help='compiler flag for both builds (repeatable)')
     ap.add_argument('units', nargs='*')
     a = ap.parse_args()
     tmp = a.keep or tempfile.mkdtemp(prefix='isa_identity_')
@@ -80,17 +83,20 @@ def main():
         ar = subprocess.run(['git', 'archive', sha, CSRC, 'include'], cwd=ROOT, check=True, capture_output=True).stdout
         subprocess.run(['tar', '-x', '-C', base], input=ar, check=True)
     differs = 0
+    variant = ''.join(re.sub(r'\W', '_', f) for f in a.define)  # kept code objects: one set per flag set
     for unit in a.units or units_of(ROOT):
         cos = []
         for tag, tree in (('base', base), ('new', ROOT)):
-            co = os.path.join(tree if tag == 'base' else tmp, '%s.%s.co' % (unit[:-4], tag))
-            if tag == 'new' or not os.path.exists(co):
-                build(tree, unit, co)
+            co = os.path.join(tree if tag == 'base' else tmp, '%s%s.%s.co' % (unit[:-4], variant, tag))
+            if tag == 'base' and not os.path.exists(os.path.join(tree, CSRC, unit)):
+                co = None   # a unit the base does not have: its kernels, if any, are reported as 'only in new'
+            elif tag == 'new' or not os.path.exists(co):
+                build(tree, unit, co, a.define)
             cos.append(co)
-        (kb, wb), (kn, wn) = kernels(cos[0]), kernels(cos[1])
-        rb, rn = resources(cos[0]), resources(cos[1])
+        (kb, wb), (kn, wn) = (kernels(cos[0]) if cos[0] else ({}, None)), kernels(cos[1])
+        rb, rn = (resources(cos[0]) if cos[0] else {}), resources(cos[1])
         names = demangle(sorted(set(kb) | set(kn)))
-        print('## %s: %s' % (unit, 'whole disassembly identical' if wb == wn else 'DIFFERS'))
+        print('## %s: %s' % (unit, 'whole disassembly identical' if wb == wn else 'not in base' if wb is None else 'DIFFERS'))
         for sym in sorted(set(kb) | set(kn)):
             if sym not in kb or sym not in kn:
                 verdict = 'only in ' + ('base' if sym in kb else 'new')

@@ -253,14 +253,9 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
             p_cur[q] = (li < ppb && i0 < n) ? src[i0] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-#ifdef NDT_BODY_STAMPS
-    unsigned long long t_mark = 0, t_acc[3] = {0ull, 0ull, 0ull};
-#endif
+    NDT_TILE_CLOCK(t_mark, t_acc);
     for (int base = blockIdx.x * ppb; base < n; base += gridDim.x * ppb) {
-#ifdef NDT_BODY_STAMPS
-        __syncthreads();
-        t_mark = __builtin_amdgcn_s_memrealtime();
-#endif
+        NDT_TILE_START(t_mark);
         float4 p[PPT];
         bool on[PPT];
 #pragma unroll
@@ -395,10 +390,8 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
         for (int q = 0; q < PPT; ++q)
 #pragma unroll
             for (int r = 0; r < NREL; ++r) c += (v[q][r] >= 0 && !(v[q][r] & kRejectBit)) ? 1 : 0;
-        NDT_BLK_STAMP(pidx, 1);
-#ifdef NDT_BODY_STAMPS
-        NDT_TILE_ACC(t_acc, t_mark, 0);
-#endif
+        NDT_BLK_STAMP(pidx, kWgProbed);
+        NDT_TILE_ACC(t_acc, t_mark, kWgSumProbe);
         int tot, own_tot = 0;
         int ofs;
         if (kOwn) {
@@ -421,10 +414,8 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
                     if (v[q][r] >= 0 && !(v[q][r] & kRejectBit)) s_pair[ofs++] = PS::pack((int)threadIdx.x + q * B, v[q][r]);
         }
         lds_barrier();
-        NDT_BLK_STAMP(pidx, 2);
-#ifdef NDT_BODY_STAMPS
-        NDT_TILE_ACC(t_acc, t_mark, 1);
-#endif
+        NDT_BLK_STAMP(pidx, kWgCompacted);
+        NDT_TILE_ACC(t_acc, t_mark, kWgSumCompact);
         pairs += tot + own_tot;
         // pair math, the next pair's record gather in flight during this pair's math.  The prefetch index is clamped
         // (unconditional load: no join of a loaded value with an undefined one right behind the load, which would
@@ -467,15 +458,11 @@ __device__ __forceinline__ void direct_pass_body(const float4* __restrict__ src,
             pair_at(own_slot, own_rec, own);
         }
         lds_barrier();
-        NDT_BLK_STAMP(pidx, 3);
-#ifdef NDT_BODY_STAMPS
-        NDT_TILE_ACC(t_acc, t_mark, 2);
-#endif
+        NDT_BLK_STAMP(pidx, kWgPaired);
+        NDT_TILE_ACC(t_acc, t_mark, kWgSumPairs);
         if (ONE_TILE) break;
     }
-#ifdef NDT_BODY_STAMPS
     NDT_TILE_ACC_STORE(pidx, t_acc);
-#endif
 }
 
 // The last-workgroup-tail pass of one registration (k_pass_direct).
@@ -514,13 +501,13 @@ __device__ __forceinline__ void pass_direct_impl(const float4* __restrict__ src,
     if (!st->pending || st->pass_kind == PASS_HESS) return;
     const int pass_idx = st->n_passes;
     if (pass_idx >= kMaxHistory) ts = nullptr;
-    if (ts && stamp0) ts[kTsStride * pass_idx] = t_entry;
+    if (ts && stamp0) ts[kTsStride * pass_idx + kTsEntry] = t_entry;
     __shared__ double red[NW * kRedStride];
     double acc[kSplitAcc];
 #pragma unroll
     for (int v = 0; v < kSplitAcc; ++v) acc[v] = 0.0;
     long long pairs = 0;
-    NDT_BLK_STAMP(pass_idx, 0);
+    NDT_BLK_STAMP(pass_idx, kWgBodyStart);
     // one set of LDS tiles shared by both grid flavours of the body
     constexpr int NREL = search_nrel(SEARCH);
     __shared__ float4 s_xt[B * PPT];
@@ -548,7 +535,7 @@ __device__ __forceinline__ void pass_direct_impl(const float4* __restrict__ src,
                                                           ts ? ts + kTsStride * pass_idx : nullptr);
     if (ts && tail) {
         __syncthreads();
-        if (threadIdx.x == 0) ts[kTsStride * pass_idx + 1] = __builtin_amdgcn_s_memrealtime();
+        if (threadIdx.x == 0) ts[kTsStride * pass_idx + kTsEnd] = __builtin_amdgcn_s_memrealtime();
     }
 }
 
@@ -582,9 +569,8 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
     constexpr int NW = B / 64;
     constexpr int kWords = sizeof(AlignState) / 8;
     static_assert(kWords <= 2 * B, "AlignState staging assumes <= 2 words per thread");
-#ifdef NDT_BODY_STAMPS
-    const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
-#endif
+    NDT_PROLOGUE_CLOCK(t_pro);  // profiling build: the prologue stamps workgroup 0 stores
+    NDT_PROLOGUE_MARK(t_pro, kProEntry);
     const int i_first = blockIdx.x * ppb + threadIdx.x;
     const bool on_first = (int)threadIdx.x < ppb && i_first < n;
     const float4 p_first[1] = {on_first ? src[i_first] : make_float4(0.f, 0.f, 0.f, 0.f)};
@@ -625,40 +611,26 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
     const unsigned long long t_start = (ts && blockIdx.x == 0 && threadIdx.x == 0) ? __builtin_amdgcn_s_memrealtime() : 0ull;
     const bool consumed = s_st.partials_pending != 0;
     __shared__ double red[kNumAcc];
-#ifdef NDT_BODY_STAMPS
-    const unsigned long long t_staged = __builtin_amdgcn_s_memrealtime();
-    unsigned long long t_reduced = t_staged;
-    // the tail stamps of workgroup 0's control step (row kBlkMax - 1 of the consumed pass)
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const int pc = s_st.n_passes;
-        g_tail_ts = pc < kBlkPasses ? &g_blk_ts[((size_t)pc * kBlkMax + kBlkMax - 1) * kBlkSlots] : nullptr;
-        g_tail_wg = 0;
-    }
-    __syncthreads();
-#endif
+    NDT_PROLOGUE_MARK(t_pro, kProStaged);
+    NDT_PROLOGUE_COPY(t_pro, kProReduced, kProStaged);  // for a kernel that consumes no partials
+    // the tail stamps of workgroup 0's control step (the tail row of the consumed pass)
+    NDT_TAIL_STAMPS_BEGIN(blockIdx.x == 0 && threadIdx.x == 0, s_st.n_passes, 0);
+    NDT_STAMP_BARRIER();
     if (s_st.partials_pending) {
         // two column pairs per lane and row: one round trip covers the 256 partial columns of a one-workgroup-per-CU
         // grid (four left half the loads predicated off; the non-zero terms are added in the same order either way):
         // C2 20.77 vs 21.10 us per pass, 1105 / 1107 vs 1089 / 1095 scans/s (same-box A/B)
         reduce_partials_pre<NW, 2, 2>(part_in, gridDim.x, pre, red);
-#ifdef NDT_BODY_STAMPS
-        t_reduced = __builtin_amdgcn_s_memrealtime();
-#endif
+        NDT_PROLOGUE_MARK(t_pro, kProReduced);
         tail_control<NW>(s_st, red, hist, blockIdx.x == 0 ? hist_cap : 0, nullptr);
         lds_barrier();
     }
-#ifdef NDT_BODY_STAMPS
-    // profiling build: workgroup 0's prologue (entry, staged, reduced, controlled) in row kBlkMax - 2 of its body's pass
-    if (blockIdx.x == 0 && threadIdx.x == 0 && s_st.n_passes < kBlkPasses) {
-        unsigned long long* r = &g_blk_ts[((size_t)s_st.n_passes * kBlkMax + kBlkMax - 2) * kBlkSlots];
-        r[0] = t_entry; r[1] = t_staged; r[2] = t_reduced; r[3] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
+    NDT_PROLOGUE_STORE(t_pro, s_st.n_passes);
     const bool body = s_st.pending && s_st.pass_kind != PASS_HESS;
     if (ts && blockIdx.x == 0 && threadIdx.x == 0) {
         const int k = s_st.n_passes;  // index of this kernel's body (the consumed pass was k - 1)
-        if (consumed && k - 1 >= 0 && k - 1 < kMaxHistory) ts[kTsStride * (k - 1) + 1] = t_start;
-        if (body && k < kMaxHistory) ts[kTsStride * k] = t_start;
+        if (consumed && k - 1 >= 0 && k - 1 < kMaxHistory) ts[kTsStride * (k - 1) + kTsEnd] = t_start;
+        if (body && k < kMaxHistory) ts[kTsStride * k + kTsEntry] = t_start;
     }
     // partials_pending of the state this kernel leaves (1: its body's partials are to be consumed).  No thread of this
     // kernel reads it again, so workgroup 0 sets it in the word it writes out; set in LDS it took a workgroup barrier of its
@@ -688,7 +660,7 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
     __shared__ int s_scan[NW];
     const int pidx = s_st.n_passes;
     const int n_pts = min(n, s_st.n_src);  // the geometry (grid, ppb) covers a point bucket >= the scan's points
-    NDT_BLK_STAMP(pidx, 0);
+    NDT_BLK_STAMP(pidx, kWgBodyStart);
     if (hdr->dense)
         direct_pass_body<SEARCH, true, B, 1, ONE_TILE>(src, n_pts, ppb, hdr, table, grid, recs, &s_st, acc, pairs, pidx, p_first, e_first, s_xt,
                                           s_pd, s_pair, s_scan, &s_st.jang[0][0], s_exp, nbr);
@@ -699,7 +671,7 @@ __global__ __launch_bounds__(pass_block(SEARCH, true, ONE_TILE)) __attribute__((
     }
     if (threadIdx.x == 32) acc[3] += (double)pairs;
     block_reduce_store_split<NW>(acc, redw, part_out + blockIdx.x, partial_stride(gridDim.x));
-    NDT_BLK_STAMP(pidx, 4);
+    NDT_BLK_STAMP(pidx, kWgBodyEnd);
 }
 #define NDT_LEAD_INST(S, ONE)                                                                                                   \
     template __global__ void k_pass_lead<S, ONE>(const float4*, int, int, const GridHeader*, const int2*, const int*, const VoxelRec*, \
@@ -899,7 +871,7 @@ __global__ __launch_bounds__(kBlock) void k_pass_radius(const float4* __restrict
     if (kind != PASS_HESS && !radius_search) return;
     const int pass_idx = st->n_passes;
     if (pass_idx >= kMaxHistory) ts = nullptr;
-    if (ts && blockIdx.x == 0 && threadIdx.x == 0) ts[kTsStride * pass_idx] = __builtin_amdgcn_s_memrealtime();
+    if (ts && blockIdx.x == 0 && threadIdx.x == 0) ts[kTsStride * pass_idx + kTsEntry] = __builtin_amdgcn_s_memrealtime();
     __shared__ double red[4 * kNumAcc];
     __shared__ __align__(16) double s_exp[kExpTabLen];
     stage_exp_tab(s_exp);
@@ -951,7 +923,7 @@ __global__ __launch_bounds__(kBlock) void k_pass_radius(const float4* __restrict
                                     ts ? ts + kTsStride * pass_idx : nullptr);
     if (ts && tail) {
         __syncthreads();
-        if (threadIdx.x == 0) ts[kTsStride * pass_idx + 1] = __builtin_amdgcn_s_memrealtime();
+        if (threadIdx.x == 0) ts[kTsStride * pass_idx + kTsEnd] = __builtin_amdgcn_s_memrealtime();
     }
 }
 
@@ -1019,16 +991,7 @@ NDT_INST(S_DIRECT1, 2, false)
 }  // namespace ndt
 
 namespace ndt {
-// host side of the profiling build's per-workgroup stamps (hipErrorNotSupported in the product build)
-hipError_t dbg_read_blk(unsigned long long* host, size_t count) {
-#ifdef NDT_BODY_STAMPS
-    if (!host) return hipSuccess;
-    const size_t n = std::min(count, (size_t)kBlkPasses * kBlkMax * kBlkSlots);
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_blk_ts), n * sizeof(unsigned long long), 0, hipMemcpyDeviceToHost);
-#else
-    (void)host;
-    (void)count;
-    return hipErrorNotSupported;
-#endif
-}
+// host side of the profiling build's per-workgroup stamps: the block table of this unit, the one whose kernels stamp
+// (hipErrorNotSupported in the product build, where kHaveBlkStamps is false and nobody calls it)
+hipError_t dbg_read_blk(unsigned long long* host, size_t count) { return read_blk_table(host, count); }
 }  // namespace ndt

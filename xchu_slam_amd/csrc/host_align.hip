@@ -210,14 +210,7 @@ AlignState* lead_state(ndt_ctx* c, int ahead) {
 ndt_status prepare_readback(ndt_ctx* c, int from, int to) {
     to = std::min(to, c->hist_cap);
     const bool prof = c->opt.profiling && to > from;
-    if (prof && !c->prof.h_ts) {  // both blocks or neither (hist_cap is fixed: made once)
-        Pinned<unsigned long long[]> h_ts;
-        Pinned<PassRecordDev[]> h_hist;
-        TRY(make_pinned(c, h_ts, kTsStride * (size_t)c->hist_cap, hipHostMallocCoherent));
-        TRY(make_pinned(c, h_hist, (size_t)c->hist_cap, hipHostMallocCoherent));
-        c->prof.h_hist = std::move(h_hist);
-        c->prof.h_ts = std::move(h_ts);
-    }
+    if (prof) TRY(ensure_stamp_copies(c));
     return NDT_OK;
 }
 
@@ -298,113 +291,6 @@ ndt_status enqueue_readback(ndt_ctx* c, int from, int to, const AlignState* d_sr
     c->al_seq = ++c->rb_seq;
     launch_readback(c, from, to, d_src, c->al_seq);
     HIPCHK(c, hipGetLastError());
-    return NDT_OK;
-}
-
-// per-pass kernel time from the in-kernel stamps (first workgroup start .. last workgroup end, 100 MHz clock)
-ndt_status collect_pass_times(ndt_ctx* c, int hist_before) {
-    const int total = std::min(c->h_state->hist_count, c->hist_cap);
-    const int ran = total - hist_before;
-    if (ran <= 0 || !c->prof.h_ts) return NDT_OK;
-    const PassRecordDev* hist = c->prof.h_hist.get() + hist_before;
-    PassProf::Stats& ps = c->prof.stats;
-    double sum = 0, bytes = 0;
-    int cnt = 0;
-    for (int k = 0; k < ran; ++k) {
-        const unsigned long long* t = &c->prof.h_ts[kTsStride * (size_t)(hist_before + k)];
-        if (t[1] <= t[0] || t[0] == ~0ull) continue;
-        sum += (double)(t[1] - t[0]) * 1e-5;  // 100 MHz ticks -> ms
-        bytes += 16.0 * c->N + 36.0 * (double)hist[k].pairs;  // B_pass = 16 N + 36 P
-        ++cnt;
-        // phases: blocks' bodies, hand-off, partials reduce, control step, state write-back / drain
-        if (t[2] >= t[0] && t[3] >= t[2] && t[4] >= t[3] && t[6] >= t[4] && t[7] >= t[6] && t[5] >= t[7] && t[1] >= t[5]) {
-            const unsigned long long e[8] = {t[0], t[2], t[3], t[4], t[6], t[7], t[5], t[1]};
-            for (int q = 0; q < 7; ++q) ps.phase_sum[q] += (double)(e[q + 1] - e[q]) * 1e-5;
-            ++ps.phase_count;
-        }
-    }
-    // profiling build: mean per-workgroup phases of this align's passes (private per-block stamps)
-    constexpr int kBP = 64, kBM = 1024, kBS = 8;
-    static const bool have_blk = dbg_read_blk(nullptr, 0) == hipSuccess;
-    std::vector<unsigned long long> blk;
-    if (have_blk) blk.resize((size_t)kBP * kBM * kBS);
-    if (have_blk && dbg_read_blk(blk.data(), blk.size()) == hipSuccess) {
-        const int nbk = std::min(direct_geom(c, c->lead != 0).nb, kBM);
-        for (int k = 0; k < ran && hist_before + k < kBP; ++k) {
-            const int pidx = hist_before + k;
-            const unsigned long long t0 = c->prof.h_ts[kTsStride * (size_t)pidx];
-            double ph[5] = {0, 0, 0, 0, 0};
-            bool ok = true;
-            int nb_used = 0;
-            for (int b = 0; b < nbk && ok; ++b) {
-                const unsigned long long* e = &blk[((size_t)pidx * kBM + b) * kBS];
-                if (e[1] == 0) continue;  // a workgroup past the scan's points (the geometry covers its size bucket)
-                if (e[1] < e[0] || e[2] < e[1] || e[3] < e[2] || e[4] < e[3]) { ok = false; break; }
-                ++nb_used;
-                // entry: from workgroup 0's pass stamp (a leading-tail kernel: after the state staging) to the body
-                ph[0] += e[0] > t0 ? (double)(e[0] - t0) : 0.0;
-                // probe / compaction / pairs: the body's per-tile sums (slots 5..7); block reduction: last tile end .. epilogue
-                for (int q = 0; q < 3; ++q) ph[1 + q] += (double)e[5 + q];
-                ph[4] += (double)(e[4] - e[3]);
-            }
-            if (!ok || nb_used == 0) continue;
-            // NDT_BLK_DUMP=file: every workgroup's body end (from the pass stamp) and per-phase ticks of pass 10
-            // (NDT_BLK_DUMP_PASS), appended
-            // (the spread of the workgroups' finish times behind the means)
-            static const char* dump = getenv("NDT_BLK_DUMP");
-            static const int dump_pass = getenv("NDT_BLK_DUMP_PASS") ? atoi(getenv("NDT_BLK_DUMP_PASS")) : 10;
-            if (dump && pidx == dump_pass) {
-                if (FILE* f = fopen(dump, "a")) {
-                    for (int b = 0; b < nbk; ++b) {
-                        const unsigned long long* e = &blk[((size_t)pidx * kBM + b) * kBS];
-                        if (e[1] == 0 || e[4] < t0) continue;
-                        fprintf(f, "%d %llu %llu %llu %llu %llu\n", b, e[0] > t0 ? e[0] - t0 : 0ull, e[4] - t0, e[5], e[6], e[7]);
-                    }
-                    fclose(f);
-                }
-            }
-            for (int q = 0; q < 5; ++q) ps.body_sum[q] += ph[q] / nb_used * 1e-5;
-            ++ps.body_count;
-            if (c->lead) {
-                // leading-tail kernels: workgroup 0's prologue (staging, partial reduction, control step + tables) in the
-                // tail slots record / machine / solve_setup
-                const unsigned long long* r = &blk[((size_t)pidx * kBM + kBM - 2) * kBS];
-                // the consumed pass's control-step stamps (tail_control, workgroup 0): [4] record done, [5] state machine
-                // done, [0]/[1] the step, [2] sin/cos, [3] tables
-                const unsigned long long* tl = pidx >= 1 ? &blk[((size_t)(pidx - 1) * kBM + kBM - 1) * kBS] : nullptr;
-                if (r[1] >= r[0] && r[2] >= r[1] && r[3] >= r[2] && r[0] > 0 && tl && tl[4] >= r[2] && tl[5] >= tl[4] &&
-                    tl[1] >= tl[5] && tl[2] >= tl[1] && tl[3] >= tl[2] && r[3] >= tl[3]) {
-                    ps.tail_sum[0] += (double)(r[1] - r[0]) * 1e-5;    // record    <- staging
-                    ps.tail_sum[1] += (double)(r[2] - r[1]) * 1e-5;    // machine   <- partial reduction
-                    ps.tail_sum[2] += (double)(tl[4] - r[2]) * 1e-5;   // solve_setup <- pass record
-                    ps.tail_sum[3] += (double)(tl[5] - tl[4]) * 1e-5;  // solve     <- state machine
-                    ps.tail_sum[4] += (double)(tl[1] - tl[5]) * 1e-5;  // post_solve <- to the step
-                    ps.tail_sum[5] += (double)(tl[2] - tl[1]) * 1e-5;  // sincos    <- step + sin/cos + barrier
-                    ps.tail_sum[6] += (double)(tl[3] - tl[2]) * 1e-5;  // rows      <- T + tables
-                    ps.tail_sum[7] += (double)(r[3] - tl[3]) * 1e-5;   // writeback <- to the body
-                    ++ps.tail_count;
-                }
-                continue;
-            }
-            // tail: [0] before / [1] after the Newton LU solve, [2] sin/cos ready, [3] tables written
-            const unsigned long long* tl = &blk[((size_t)pidx * kBM + kBM - 1) * kBS];
-            const unsigned long long* t = &c->prof.h_ts[kTsStride * (size_t)pidx];
-            if (tl[4] >= t[6] && tl[5] >= tl[4] && tl[0] >= tl[5] && tl[1] >= tl[0] && t[7] >= tl[1] && tl[2] >= t[7] &&
-                tl[3] >= tl[2] && t[5] >= tl[3]) {
-                const unsigned long long e[9] = {t[6], tl[4], tl[5], tl[0], tl[1], t[7], tl[2], tl[3], t[5]};
-                for (int q = 0; q < 8; ++q) ps.tail_sum[q] += (double)(e[q + 1] - e[q]) * 1e-5;
-                // the speculative Newton solve on wave 0: its start after staging, its duration
-                if (tl[6] >= t[6] && tl[7] >= tl[6]) {
-                    ps.tail_sum[8] += (double)(tl[6] - t[6]) * 1e-5;
-                    ps.tail_sum[9] += (double)(tl[7] - tl[6]) * 1e-5;
-                }
-                ++ps.tail_count;
-            }
-        }
-    }
-    ps.ms_sum += sum;
-    ps.bytes_sum += bytes;
-    ps.count += cnt;
     return NDT_OK;
 }
 

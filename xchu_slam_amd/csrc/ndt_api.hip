@@ -147,32 +147,6 @@ ndt_status ndt_synchronize(ndt_ctx* c) {
     return NDT_OK;
 }
 
-ndt_status ndt_last_timings(ndt_ctx* c, double* ms_build, double* ms_align, double* ms_pass_avg, double* pass_bytes_avg) {
-    if (!c) return NDT_EINVAL;
-    if (ms_build) *ms_build = c->ms_build;
-    if (ms_align) *ms_align = c->ms_align;
-    // pass statistics over this ctx and the helper contexts of ndt_align_batch (the batch's other streams)
-    double ms = c->prof.stats.ms_sum, bytes = c->prof.stats.bytes_sum;
-    long long cnt = c->prof.stats.count;
-    for (const ndt_ctx* h : c->helpers) {
-        ms += h->prof.stats.ms_sum;
-        bytes += h->prof.stats.bytes_sum;
-        cnt += h->prof.stats.count;
-    }
-    if (ms_pass_avg) *ms_pass_avg = cnt ? ms / cnt : 0.0;
-    if (pass_bytes_avg) *pass_bytes_avg = cnt ? bytes / cnt : 0.0;
-    return NDT_OK;
-}
-
-ndt_status ndt_pass_phases(ndt_ctx* c, double ms[22]) {
-    if (!c || !ms) return NDT_EINVAL;
-    const PassProf::Stats& ps = c->prof.stats;
-    for (int q = 0; q < 7; ++q) ms[q] = ps.phase_count ? ps.phase_sum[q] / ps.phase_count : 0.0;
-    for (int q = 0; q < 5; ++q) ms[7 + q] = ps.body_count ? ps.body_sum[q] / ps.body_count : 0.0;
-    for (int q = 0; q < 10; ++q) ms[12 + q] = ps.tail_count ? ps.tail_sum[q] / ps.tail_count : 0.0;
-    return NDT_OK;
-}
-
 ndt_status ndt_set_pass_options(ndt_ctx* c, int lead_tail, int points_per_thread, int source_order) {
     if (!c || lead_tail < 0 || lead_tail > 1 || points_per_thread < 1 || points_per_thread > 3 || source_order < 0 ||
         source_order > 1)
@@ -215,16 +189,6 @@ ndt_status ndt_build_stats(ndt_ctx* c, long long out[6]) {
         out[3] += h->n_rerun_lookback;
         out[4] += h->opt.tile_tickets ? 1 : 0;
     }
-    return NDT_OK;
-}
-
-ndt_status ndt_set_profiling(ndt_ctx* c, int enable) {
-    if (!c) return NDT_EINVAL;
-    for (ndt_ctx* h : c->helpers) TRY(ndt_set_profiling(h, enable));
-    c->opt.profiling = enable != 0;
-    c->prof.stats = PassProf::Stats{};
-    // no graph invalidation: the profiling flag and the stamp buffer are part of every graph's cache key, so a call
-    // that only resets the statistics keeps the captured chains
     return NDT_OK;
 }
 

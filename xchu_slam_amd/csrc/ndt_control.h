@@ -6,6 +6,8 @@
 // then builds the next transform and angle tables with the six sin/cos evaluations spread over lanes.
 #pragma once
 #include "ndt_device.h"
+#define NDT_STAMPS_DEVICE  // the kernels of this header stamp: the device helpers of ndt_stamps.h
+#include "ndt_stamps.h"
 
 namespace ndt {
 
@@ -410,22 +412,22 @@ __device__ __forceinline__ void solve_loop(AlignState* st, const double* spec_dp
         if (!st->want_solve) break;
         if (spec_dp) {
             if (threadIdx.x == 0) {
-                NDT_TAIL_STAMP(0);
-                NDT_TAIL_STAMP(1);
+                NDT_TAIL_STAMP(kTailSolveBegin);
+                NDT_TAIL_STAMP(kTailSolveEnd);
                 newton_after_solve(st, spec_dp, *spec_fail);
             }
             continue;
         }
         if (threadIdx.x < 6) s_mg[threadIdx.x] = -st->g[threadIdx.x];
         lds_barrier();
-        if (threadIdx.x == 0) NDT_TAIL_STAMP(0);
+        if (threadIdx.x == 0) NDT_TAIL_STAMP(kTailSolveBegin);
         if (threadIdx.x < 64) {
             const int f = lu6_solve_rows(st->H, s_mg, s_dp, false);
             if (threadIdx.x == 0) s_fail = f;
         }
         lds_barrier();
         if (threadIdx.x == 0) {
-            NDT_TAIL_STAMP(1);
+            NDT_TAIL_STAMP(kTailSolveEnd);
             newton_after_solve(st, s_dp, s_fail);
         }
     }
@@ -465,7 +467,7 @@ __device__ void pass_tables(AlignState* st, const double* s_sc) {
     }
     if (t == 0) st->needs_tables = 0;
     lds_barrier();
-    if (t == 0) NDT_TAIL_STAMP(3);
+    if (t == 0) NDT_TAIL_STAMP(kTailRows);
 }
 
 // convertTransform(x_t) -> T and computeAngleDerivatives(x_t) -> tables, for a workgroup: wave 0 lanes 0-2
@@ -492,7 +494,7 @@ __device__ void prepare_pass_parallel(AlignState* st) {
         s_sc[6 + 2 * lane + 1] = c;
     }
     lds_barrier();
-    if (t == 0) NDT_TAIL_STAMP(2);
+    if (t == 0) NDT_TAIL_STAMP(kTailSinCos);
     pass_tables<NW>(st, s_sc);
 }
 
@@ -734,18 +736,18 @@ __device__ __forceinline__ void tail_control(AlignState& s_st, const double* red
     double x_lu[6];
     if (wv == 0) {
         if (spec) {
-            if (threadIdx.x == 0) NDT_TAIL_STAMP(6);
+            if (threadIdx.x == 0) NDT_TAIL_STAMP(kTailSpecBegin);
             const int f = lu6_solve_rows(red + 7, red + 1, s_spec_dp, true, x_lu);
             if (threadIdx.x == 0) {
                 s_spec_fail = f;
-                NDT_TAIL_STAMP(7);
+                NDT_TAIL_STAMP(kTailSpecEnd);
             }
         }
     } else if (wv == 1) {
         control_record_wave(&s_st, red, hist, hist_cap);
-        if ((threadIdx.x & 63) == 0) NDT_TAIL_STAMP(4);
+        if ((threadIdx.x & 63) == 0) NDT_TAIL_STAMP(kTailRecord);
         control_step_wave(&s_st, red);
-        if ((threadIdx.x & 63) == 0) NDT_TAIL_STAMP(5);
+        if ((threadIdx.x & 63) == 0) NDT_TAIL_STAMP(kTailMachine);
     }
     bool tables_done = false;
     // Fast path (the Newton step after a speculatively solved direction, nearly every pass): after the state machine
@@ -850,17 +852,17 @@ __device__ __forceinline__ void tail_control(AlignState& s_st, const double* red
         }
         lds_barrier();
         if (s_go3) {
-            if (ts && threadIdx.x == 0) ts[7] = __builtin_amdgcn_s_memrealtime();
-            if (threadIdx.x == 0) { NDT_TAIL_STAMP(0); NDT_TAIL_STAMP(1); NDT_TAIL_STAMP(2); NDT_TAIL_STAMP(3); }
+            if (ts && threadIdx.x == 0) ts[kTsControl] = __builtin_amdgcn_s_memrealtime();
+            if (threadIdx.x == 0) { NDT_TAIL_STAMP(kTailSolveBegin); NDT_TAIL_STAMP(kTailSolveEnd); NDT_TAIL_STAMP(kTailSinCos); NDT_TAIL_STAMP(kTailRows); }
             tables_done = true;
         }
     }
     if (!tables_done) {
         solve_loop(&s_st, spec ? s_spec_dp : nullptr, &s_spec_fail);
-        if (ts && threadIdx.x == 0) ts[7] = __builtin_amdgcn_s_memrealtime();
+        if (ts && threadIdx.x == 0) ts[kTsControl] = __builtin_amdgcn_s_memrealtime();
         if (s_st.needs_tables) prepare_pass_parallel<NW>(&s_st);
     }
-    if (ts && threadIdx.x == 0) ts[5] = __builtin_amdgcn_s_memrealtime();
+    if (ts && threadIdx.x == 0) ts[kTsTables] = __builtin_amdgcn_s_memrealtime();
 }
 
 // Epilogue of every derivative pass (all threads of every workgroup call it); returns true in the workgroup that ran
@@ -884,9 +886,7 @@ __device__ __forceinline__ bool pass_handoff(AlignState* st, double* partials, u
     // profiling stamps are single plain stores (no atomics on shared words): the pass start by workgroup 0 (dispatched
     // first), everything else by the last workgroup (the last body to finish draws the last ticket)
     const unsigned long long t_body = ts ? __builtin_amdgcn_s_memrealtime() : 0ull;
-#ifdef NDT_BODY_STAMPS
-    NDT_BLK_STAMP(st->n_passes, 4);
-#endif
+    NDT_BLK_STAMP(st->n_passes, kWgBodyEnd);
     __shared__ unsigned s_ticket;
     __shared__ double red[kNumAcc];
     // two-level hand-off (grids of more than kTwoLevelMinBlocks workgroups, e.g. one 256-point tile per workgroup over a
@@ -923,11 +923,11 @@ __device__ __forceinline__ bool pass_handoff(AlignState* st, double* partials, u
     }
     __syncthreads();
     if (s_ticket != (two ? (unsigned)ng : gridDim.x) - 1) return false;
-    if (ts && threadIdx.x == 0) ts[2] = t_body;
+    if (ts && threadIdx.x == 0) ts[kTsBodyEnd] = t_body;
     if (threadIdx.x == 0) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (ts) ts[3] = __builtin_amdgcn_s_memrealtime();
+        if (ts) ts[kTsAcquired] = __builtin_amdgcn_s_memrealtime();
     }
     __syncthreads();
     // the optimiser state is fetched together with the partials (one memory round trip for both)
@@ -940,16 +940,10 @@ __device__ __forceinline__ bool pass_handoff(AlignState* st, double* partials, u
         if ((int)threadIdx.x < kWords) sv0 = gw[threadIdx.x];
         if ((int)threadIdx.x + B < kWords) sv1 = gw[threadIdx.x + B];
     }
-#ifdef NDT_BODY_STAMPS
-    if (threadIdx.x == 0) {
-        const int p = st->n_passes;
-        g_tail_ts = p < kBlkPasses ? &g_blk_ts[((size_t)p * kBlkMax + kBlkMax - 1) * kBlkSlots] : nullptr;
-        g_tail_wg = blockIdx.x;
-    }
-#endif
+    NDT_TAIL_STAMPS_BEGIN(threadIdx.x == 0, st->n_passes, blockIdx.x);
     if (two) reduce_partials_block<NW, K>(gpart, ng, red, kMaxGroups);
     else reduce_partials_block<NW, K>(partials, gridDim.x, red);
-    if (ts && threadIdx.x == 0) ts[4] = __builtin_amdgcn_s_memrealtime();
+    if (ts && threadIdx.x == 0) ts[kTsReduced] = __builtin_amdgcn_s_memrealtime();
     if (mode == 1) {
         if (threadIdx.x < kNumAcc) red_out[threadIdx.x] = red[threadIdx.x];
         if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -960,7 +954,7 @@ __device__ __forceinline__ bool pass_handoff(AlignState* st, double* partials, u
     if ((int)threadIdx.x < kWords) lw[threadIdx.x] = sv0;
     if ((int)threadIdx.x + B < kWords) lw[threadIdx.x + B] = sv1;
     lds_barrier();
-    if (ts && threadIdx.x == 0) ts[6] = __builtin_amdgcn_s_memrealtime();
+    if (ts && threadIdx.x == 0) ts[kTsStaged] = __builtin_amdgcn_s_memrealtime();
     tail_control<NW>(s_st, red, hist, hist_cap, ts);
     for (int k = threadIdx.x; k < kWords; k += B) gw[k] = lw[k];
     if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

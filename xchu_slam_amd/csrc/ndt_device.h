@@ -68,43 +68,6 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int* lds /*[NW]*/, in
     return wofs + x - v;
 }
 
-
-// Profiling build only (-DNDT_BODY_STAMPS, `make VARIANT=dbg`): per-workgroup phase stamps of the first
-// kBlkPasses passes, plain stores into private slots (no contention), read back by ndt_dbg_read_blk.
-#ifdef NDT_BODY_STAMPS
-constexpr int kBlkPasses = 64, kBlkMax = 1024, kBlkSlots = 8;
-static __device__ unsigned long long g_blk_ts[kBlkPasses * kBlkMax * kBlkSlots];
-// per-tile phase sums of one workgroup (probe, compaction, pairs), stored into slots 5..7 at the end of the body
-#define NDT_TILE_ACC(acc, mark, k)                                        \
-    do {                                                                  \
-        __syncthreads();                                                  \
-        const unsigned long long _n = __builtin_amdgcn_s_memrealtime();   \
-        (acc)[k] += _n - (mark);                                          \
-        (mark) = _n;                                                      \
-    } while (0)
-#define NDT_TILE_ACC_STORE(pass, acc)                                                                          \
-    do {                                                                                                       \
-        if (threadIdx.x == 0 && (pass) >= 0 && (pass) < kBlkPasses && blockIdx.x < kBlkMax)                     \
-            for (int _k = 0; _k < 3; ++_k) g_blk_ts[((size_t)(pass) * kBlkMax + blockIdx.x) * kBlkSlots + 5 + _k] = (acc)[_k]; \
-    } while (0)
-#define NDT_BLK_STAMP(pass, slot)                                                                            \
-    do {                                                                                                     \
-        __syncthreads();                                                                                     \
-        if (threadIdx.x == 0 && (pass) >= 0 && (pass) < kBlkPasses && blockIdx.x < kBlkMax)                   \
-            g_blk_ts[((size_t)(pass) * kBlkMax + blockIdx.x) * kBlkSlots + (slot)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-// the last workgroup's tail of pass p stamps into the unused workgroup row kBlkMax-1 of pass p
-static __device__ unsigned long long* g_tail_ts;
-static __device__ unsigned g_tail_wg;  // the workgroup whose tail stamps g_tail_ts (leading-tail kernels: workgroup 0)
-#define NDT_TAIL_STAMP(slot)                                                  \
-    do {                                                                      \
-        if (g_tail_ts && g_tail_wg == blockIdx.x) g_tail_ts[(slot)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#else
-#define NDT_BLK_STAMP(pass, slot) do { } while (0)
-#define NDT_TAIL_STAMP(slot) do { } while (0)
-#endif
-
 __device__ __forceinline__ double shfl_xor_d(double v, int m) {
     return __shfl_xor(v, m, 64);
 }

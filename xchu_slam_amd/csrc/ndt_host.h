@@ -21,6 +21,7 @@
 #include "../../include/ndt_hip.h"
 #include "ndt_kernels.h"
 #include "ndt_geom.h"
+#include "ndt_stamps.h"
 
 namespace ndt::host {
 
@@ -204,22 +205,14 @@ struct FrontEnd {
     size_t nvox = 0;
 };
 
-// host_align.hip (and the two profiling entry points) — pass profiling: the stamp buffer and its pinned copies, which
-// are part of every graph's cache key and stay, and the statistics ndt_set_profiling resets
+// host_prof.hip — pass profiling: the stamp buffer (host_align.hip's launches carry it) and its pinned copies, which
+// are part of every graph's cache key and stay, and the statistics ndt_set_profiling resets (ndt_stamps.h)
 struct PassProf {
-    DevBuf<unsigned long long> ts;      // per-pass kTsStride s_memrealtime stamps
+    DevBuf<unsigned long long> ts;      // the pass rows: kTsStride s_memrealtime stamps per pass
     Pinned<unsigned long long[]> h_ts;  // pinned copies, filled by k_readback before the align's sync (made together)
     Pinned<PassRecordDev[]> h_hist;
-    struct Stats {
-        double phase_sum[7] = {0, 0, 0, 0, 0, 0, 0};
-        int phase_count = 0;
-        double body_sum[5] = {0, 0, 0, 0, 0};
-        int body_count = 0;
-        double tail_sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        int tail_count = 0;
-        double ms_sum = 0, bytes_sum = 0;
-        long long count = 0;
-    } stats;
+    using Stats = PassStats;
+    Stats stats;
 };
 
 // host_icp.hip — point-to-point ICP (ndt_icp_align): the cumulative cloud X, per-point match / d2 of the last pass, the
@@ -580,6 +573,9 @@ ndt_status keyed_graph(ndt_ctx* c, KeyedGraph<N>& g, const long long (&key)[N], 
     *out = g.exec.get();
     return NDT_OK;
 }
+// host_prof.hip
+ndt_status ensure_stamp_copies(ndt_ctx* c);
+ndt_status collect_pass_times(ndt_ctx* c, int hist_before);
 // host_lanes.hip
 ndt_status main_after_fit(ndt_ctx* c, bool source);
 ndt_status enqueue_nn_index(ndt_ctx* c, Lane L, const float4* pts, int n, int dense, float cell, NNIndex& ix, bool want_idx = false);

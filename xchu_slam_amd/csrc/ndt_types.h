@@ -60,9 +60,6 @@ constexpr int kTwoLevelMinBlocks = 1024;
 __host__ __device__ constexpr int group_size(int nb) {
     return nb / kMaxGroups >= 64 ? (((nb + kMaxGroups - 1) / kMaxGroups + 1) & ~1) : 64;
 }
-// profiling stamps per pass (s_memrealtime, 100 MHz): [0] start(min), [1] end(max), [2] last body done(max),
-// [3] tail acquired, [4] tail reduced, [6] state staged in LDS, [7] control step done, [5] next pass prepared
-constexpr int kTsStride = 16;
 // radix sort auxiliaries: kRadixCopies copies of the [4 digit positions][256] global digit counts (workgroup b of the key
 // kernel adds into copy b % kRadixCopies, so that fewer workgroups contend for one counter; the passes sum the copies)
 // + 4 tile tickets (ticket-ordered passes)

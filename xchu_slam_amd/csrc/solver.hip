@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kBlock) void k_svd_resume(AlignState* st) {
 
 // Start of an align in one launch (instead of a state upload, a ticket-counter memset and a stamp memset + init):
 // the host-built state arrives as the kernel argument, the pass ticket counters are zeroed, and (profiling) the
-// stamp rows are reset — slot 0 of each row to ~0 (a min), the others to 0.
+// stamp rows are reset — the entry slot of each row to kTsUnstamped, the others to 0 (ndt_stamps.h).
 static_assert(sizeof(AlignState) <= 3072, "AlignState travels as a kernel argument (4 KB limit)");
 __global__ void k_align_init(const AlignState st, AlignState* __restrict__ d_state, unsigned* __restrict__ counter,
                              unsigned long long* __restrict__ ts, int ts_words, unsigned long long* __restrict__ clk,
@@ -88,7 +88,7 @@ __global__ void k_align_init(const AlignState st, AlignState* __restrict__ d_sta
         }
     }
     if (ts)
-        for (int k = i; k < ts_words; k += gridDim.x * kBlock) ts[k] = (k % kTsStride) == 0 ? ~0ull : 0ull;
+        for (int k = i; k < ts_words; k += gridDim.x * kBlock) ts[k] = (k % kTsStride) == kTsEntry ? kTsUnstamped : 0ull;
 }
 
 // End-of-round read-back into pinned host memory by one workgroup: the optimiser state and, when profiling, the stamps
