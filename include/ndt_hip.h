@@ -28,7 +28,9 @@ extern "C" {
  * ndt_pass_geometry (its 8 ints); no earlier layout changed; ground surface added at 6, size-checked (ndt_ground_params and
  * ndt_ground_result start with their own size, which the library checks; no earlier layout changed); position factors of
  * the pose graph added at 6 (ndt_pgo_add_position, ndt_pgo_get_position_weights: two functions, no struct or buffer layout
- * of their own; no earlier layout changed); ndt_pgo_set_estimate added at 6 (one function, no layout of its own).  A caller built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
+ * of their own; no earlier layout changed); ndt_pgo_set_estimate added at 6 (one function, no layout of its own); the
+ * pose graph's solver choice added at 6 (ndt_pgo_set_solver, ndt_pgo_get_solver, ndt_pgo_solver_stats with its own
+ * ndt_pgo_solver_stats_t; no earlier layout changed).  A caller built against this header checks ndt_abi_version() == NDT_HIP_ABI_VERSION before its first call. */
 #define NDT_HIP_ABI_VERSION 6
 
 typedef struct ndt_ctx ndt_ctx;
@@ -506,6 +508,27 @@ ndt_status ndt_pgo_get_weights(ndt_pgo* pgo, double* w, int cap, int* n_out);
 ndt_status ndt_pgo_get_position_weights(ndt_pgo* pgo, double* w, int cap, int* n_out);
 /* One record per step of the last optimise. */
 ndt_status ndt_pgo_history(ndt_pgo* pgo, ndt_pgo_record* out, int cap, int* n_out);
+
+/* The linear solver of each Gauss-Newton step.  CG (the default): conjugate gradients inside the one launch.  DIRECT: the
+ * rank-d part of the normal equations (d = 6 x between factors + 3 x position factors) is factorised exactly as a dense
+ * d x d matrix, a fixed sequence of launches per step; same inputs, same warm start, max_iter and step_eps, same errors,
+ * weights and history; cg_iterations is 0 in the result and in every record, cg_max_iter and cg_rtol are ignored.  A DIRECT
+ * optimise with d > 8192 is NDT_EINVAL and leaves the estimate unchanged. */
+#define NDT_PGO_SOLVER_CG 0
+#define NDT_PGO_SOLVER_DIRECT 1
+typedef struct {
+    int solver;                      /* the solver the last optimise used                                            */
+    int d;                           /* 6 m + 3 np of that graph                                                     */
+    int tile;                        /* DIRECT: tile width of the blocked factorisation (CG: 0)                      */
+    int factorizations;              /* DIRECT: factorisations run, one per step                                     */
+    int refined;                     /* DIRECT: 1 when a refinement pass ran after each solve                        */
+} ndt_pgo_solver_stats_t;
+/* Host state only: the solver of later optimises.  An unknown value is NDT_EINVAL. */
+ndt_status ndt_pgo_set_solver(ndt_pgo* pgo, int solver);
+int ndt_pgo_get_solver(const ndt_pgo* pgo);              /* -1 for a NULL handle */
+/* Of the last optimise whose launches ran, whether it returned NDT_OK or found a rotation at pi or a non-finite value (all
+ * zero before the first; an optimise refused before its launches, or ended by a device error, leaves them as they were). */
+ndt_status ndt_pgo_solver_stats(ndt_pgo* pgo, ndt_pgo_solver_stats_t* out);
 
 /* ---- Global map: what pgo_node builds three times from its keyframes and their current poses (pgo_node.cpp) — SaveMap
  * (:620-653, every keyframe, finalMap.pcd), PublishPoseAndFrame (:744-812, every second keyframe, again as the graph

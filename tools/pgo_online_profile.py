@@ -3,6 +3,7 @@
 
     python tools/pgo_online_profile.py                       # online "predict", online "optimize", batch; one JSON line
     python tools/pgo_online_profile.py --keyframes 300       # a prefix of the workload
+    python tools/pgo_online_profile.py --solver direct --only predict    # PoseGraph's linear solver; one part alone
 
 The workload: 1541 keyframes (the reference run's keyframe count) taken evenly from the KITTI-00 ground-truth trajectory
 (tests/golden/kitti00_gt.npz, the selection of tools/pgo_profile.py and tools/globalmap_profile.py), each a synthetic
@@ -67,12 +68,12 @@ def errors(xa, poses, true):
     return {"ape_rmse_m": a["rmse"], "ape_max_m": a["max"], "rpe_rmse_m": r["rmse"]}
 
 
-def online(xa, true, odom, keyframes, append):
-    with xa.PGO(keyframe_gap=-1.0, detect_args=DETECT, append=append, **REFINE) as pgo:
+def online(xa, true, odom, keyframes, append, solver="cg"):
+    with xa.PGO(keyframe_gap=-1.0, detect_args=DETECT, append=append, solver=solver, **REFINE) as pgo:
         pgo.sync_timings = True
         pgo.keep_poses_before = False
         split = dict.fromkeys(("store", "detect", "refine", "optimize"), 0.0)
-        worst = 0.0
+        worst, solve_ms = 0.0, []
         t0 = time.perf_counter()
         for k, (cloud, pose) in enumerate(zip(keyframes, odom)):
             t1 = time.perf_counter()
@@ -80,11 +81,14 @@ def online(xa, true, odom, keyframes, append):
             worst = max(worst, time.perf_counter() - t1)
             for name, ms in rec["ms"].items():
                 split[name] += ms
+            if rec["info"]:
+                solve_ms.append(rec["ms"]["optimize"])
             if k % 200 == 199:
                 print(f"{append}: {k + 1} keyframes, {time.perf_counter() - t0:.1f} s, {len(pgo.loops)} loops", file=sys.stderr, flush=True)
         total = time.perf_counter() - t0
         solves = [r["info"] for r in pgo.log if r["info"]]
-        out = {"append": append, "s_total": total, "ms_per_keyframe": 1e3 * total / len(odom), "ms_worst_keyframe": 1e3 * worst,
+        out = {"append": append, "solver": solver, "ms_mean_solve": float(np.mean(solve_ms)) if solve_ms else 0.0,
+               "ms_worst_solve": max(solve_ms, default=0.0), "d_last": pgo._graph.solver_stats()["d"], "s_total": total, "ms_per_keyframe": 1e3 * total / len(odom), "ms_worst_keyframe": 1e3 * worst,
                "s_split": {k: v / 1e3 for k, v in split.items()}, "candidates": sum(1 for r in pgo.log if r["candidate"] != -1),
                "refined": sum(1 for r in pgo.log if r["refined"]), "accepted": len(pgo.loops),
                "gate_rejected": sum(1 for r in pgo.rejected if r[2] == "pair_distance"),
@@ -94,7 +98,7 @@ def online(xa, true, odom, keyframes, append):
         return out
 
 
-def batch(xa, true, odom, keyframes):
+def batch(xa, true, odom, keyframes, solver="cg"):
     from xchu_slam_amd import synth
     from xchu_slam_amd.posegraph import _matrix_to_pose6d
     with xa.KeyframeMap() as store:
@@ -112,9 +116,9 @@ def batch(xa, true, odom, keyframes):
         not_rigid = sum(1 for Rm in raw if np.abs(Rm.T @ Rm - np.eye(3)).max() > 1e-6)
         accepted = [(i, j, synth.pose_matrix(*_matrix_to_pose6d(np.asarray(T, np.float64))), s) for i, j, T, s in accepted]
         t0 = time.perf_counter()
-        poses, info = xa.optimize_loops(odom, accepted, registration=store.registration)
+        poses, info = xa.optimize_loops(odom, accepted, registration=store.registration, solver=solver)
         t_opt = time.perf_counter() - t0
-    out = {"s_store": t_store, "s_close_loops": t_close, "s_optimize_loops": t_opt, "s_total": t_store + t_close + t_opt,
+    out = {"solver": solver, "s_store": t_store, "s_close_loops": t_close, "s_optimize_loops": t_opt, "s_total": t_store + t_close + t_opt,
            "accepted": len(accepted), "transforms_not_rigid_to_1e-6": not_rigid, "rejected_icp": sum(1 for r in rejected if r[2] == "icp"),
            "gate_rejected": sum(1 for r in rejected if r[2] == "pair_distance"), "iterations": info["iterations"],
            "converged": info["converged"], "cg_iterations": info["cg_iterations"]}
@@ -125,15 +129,22 @@ def batch(xa, true, odom, keyframes):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--keyframes", type=int, default=N_KEYFRAMES)
+    ap.add_argument("--solver", default="cg", help="PoseGraph's linear solver: cg, direct, or both (each part run with cg, then direct)")
+    ap.add_argument("--only", default="", help="comma-separated parts to run (predict, optimize, batch); default: all three")
     a = ap.parse_args()
     import xchu_slam_amd as xa
     t0 = time.perf_counter()
     true, odom, keyframes = workload(a.keyframes)
     res = {"keyframes": len(odom), "points_per_keyframe": N_POINTS, "s_generate": time.perf_counter() - t0,
            "odometry": errors(xa, odom, true)}
-    for name, run in (("predict", lambda: online(xa, true, odom, keyframes, "predict")),
-                      ("optimize", lambda: online(xa, true, odom, keyframes, "optimize")),
-                      ("batch", lambda: batch(xa, true, odom, keyframes))):
-        res[name] = run()
-        print(name, json.dumps(res[name]), file=sys.stderr, flush=True)      # each part as it finishes
+    parts = {"predict": lambda sv: online(xa, true, odom, keyframes, "predict", sv),
+             "optimize": lambda sv: online(xa, true, odom, keyframes, "optimize", sv),
+             "batch": lambda sv: batch(xa, true, odom, keyframes, sv)}
+    for name in (a.only.split(",") if a.only else parts):
+        for sv in (("cg", "direct") if a.solver == "both" else (a.solver,)):
+            key = name if a.solver != "both" else f"{name}_{sv}"
+            while key in res:        # a part named twice (--only predict,predict) runs twice, alternating the solvers
+                key += "+"
+            res[key] = parts[name](sv)
+            print(key, json.dumps(res[key]), file=sys.stderr, flush=True)      # each part as it finishes
     print(json.dumps(res))

@@ -74,12 +74,12 @@ def rms(A, B):
     return float(np.sqrt(((A - B)[:, :3, 3] ** 2).sum(1).mean()))
 
 
-def device(altitude=False):
+def device(altitude=False, solver="cg"):
     import xchu_slam_amd as xa
     true, est, loops = graph()
-    wall, info, hist, X = [], None, None, None
+    wall, info, hist, X, stats = [], None, None, None, None
     for _ in range(WARMUP + REPEATS):
-        with xa.PoseGraph() as pg:
+        with xa.PoseGraph(solver=solver) as pg:
             for P in est:
                 pg.add_node(P)
             for i, j, Z, var, k in loops:
@@ -90,18 +90,27 @@ def device(altitude=False):
             t0 = time.perf_counter()
             info = pg.optimize()
             wall.append((time.perf_counter() - t0) * 1e3)
-            hist, X = pg.history(), pg.poses()
-    print(json.dumps({"nodes": len(est), "loops": len(loops), "positions": len(est) if altitude else 0, "ms_wall_call": float(statistics.median(wall[WARMUP:])), "info": info,
+            hist, X, stats = pg.history(), pg.poses(), pg.solver_stats()
+    print(json.dumps({"solver": stats, "ms_per_outer_iteration": float(statistics.median(wall[WARMUP:])) / max(1, info["iterations"]), "nodes": len(est), "loops": len(loops), "positions": len(est) if altitude else 0, "ms_wall_call": float(statistics.median(wall[WARMUP:])), "info": info,
                       "cg_per_iteration": [r["cg_iterations"] for r in hist], "rms_in_m": rms(est, true), "rms_out_m": rms(X, true),
                       "z_rms_in_m": float(np.sqrt(((est - true)[:, 2, 3] ** 2).mean())), "z_rms_out_m": float(np.sqrt(((X - true)[:, 2, 3] ** 2).mean()))}))
 
 
 def summarise(path):
-    v = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
-         if "k_pgo_optimize" in r["Kernel_Name"]]
-    assert len(v) == WARMUP + REPEATS, len(v)
-    v = v[WARMUP:]
-    print(f"k_pgo_optimize  n {len(v)}  median {statistics.median(v):.3f} ms  min {min(v):.3f}  max {max(v):.3f}")
+    rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
+    v = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in rows if "k_pgo_optimize" in r["Kernel_Name"]]
+    if v:
+        assert len(v) == WARMUP + REPEATS, len(v)
+        v = v[WARMUP:]
+        print(f"k_pgo_optimize  n {len(v)}  median {statistics.median(v):.3f} ms  min {min(v):.3f}  max {max(v):.3f}")
+    # the direct solve's kernels: dispatches and device time summed over the whole run (WARMUP + REPEATS optimises)
+    per = {}
+    for r in rows:
+        name = r["Kernel_Name"].split("(")[0].split("::")[-1]
+        if name.startswith(("k_pgo_direct", "k_pgo_schur", "k_pgo_chol")):
+            per.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for name, us in per.items():
+        print(f"{name}  n {len(us)}  total {sum(us) / 1e3:.3f} ms  median {statistics.median(us):.2f} us  max {max(us):.2f} us")
 
 
 def restatement():
@@ -119,6 +128,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--restatement", action="store_true")
     ap.add_argument("--altitude", action="store_true")
+    ap.add_argument("--solver", default="cg", choices=("cg", "direct"), help="PoseGraph's linear solver")
     ap.add_argument("--summarise", metavar="KERNEL_TRACE_CSV", default="")
     a = ap.parse_args()
     if a.summarise:
@@ -126,4 +136,4 @@ if __name__ == "__main__":
     elif a.restatement:
         restatement()
     else:
-        device(a.altitude)
+        device(a.altitude, a.solver)

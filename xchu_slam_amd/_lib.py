@@ -275,6 +275,19 @@ class PgoRecord(C.Structure):
     ]
 
 
+class PgoSolverStats(C.Structure):
+    _fields_ = [
+        ("solver", C.c_int),
+        ("d", C.c_int),
+        ("tile", C.c_int),
+        ("factorizations", C.c_int),
+        ("refined", C.c_int),
+    ]
+
+
+# NDT_PGO_SOLVER_*
+PGO_SOLVER_CG, PGO_SOLVER_DIRECT = range(2)
+
 # ndt_icp_state
 ICP_NOT_CONVERGED, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
 # ndt_gicp_state
@@ -408,6 +421,9 @@ SIGNATURES = {
     "ndt_pgo_get_weights": (C.c_int, [_P, _DP, C.c_int, C.POINTER(C.c_int)]),
     "ndt_pgo_get_position_weights": (C.c_int, [_P, _DP, C.c_int, C.POINTER(C.c_int)]),
     "ndt_pgo_history": (C.c_int, [_P, C.POINTER(PgoRecord), C.c_int, C.POINTER(C.c_int)]),
+    "ndt_pgo_set_solver": (C.c_int, [_P, C.c_int]),
+    "ndt_pgo_get_solver": (C.c_int, [_P]),
+    "ndt_pgo_solver_stats": (C.c_int, [_P, C.POINTER(PgoSolverStats)]),
     "ndt_map_create": (C.c_int, [_P, C.POINTER(_P)]),
     "ndt_map_destroy": (None, [_P]),
     "ndt_map_size": (C.c_int, [_P]),

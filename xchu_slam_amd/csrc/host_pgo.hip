@@ -1,7 +1,10 @@
 // host_pgo.hip — the pose graph on a ctx (pgo_node's GTSAM back end as a batch problem): ndt_pgo_*.
 // The host keeps the graph (a few hundred KB at KITTI-00's 1541 keyframes) and the estimate; ndt_pgo_optimize uploads
-// them, runs the whole optimisation as one launch on the ctx stream and reads the result back once.
+// them, runs the whole optimisation as one launch on the ctx stream and reads the result back once.  Under
+// NDT_PGO_SOLVER_DIRECT (ndt_pgo_set_solver) an outer iteration is a fixed sequence of launches instead
+// (posegraph_direct.hip) and the host reads a small status block after each.
 #include "ndt_host.h"
+#include "ndt_pgo_schur.h"
 
 struct ndt_pgo {
     ndt_ctx* c = nullptr;
@@ -16,6 +19,10 @@ struct ndt_pgo {
     DevBuf<int> d_i32;
     DevBuf<ndt_pgo_record> d_hist;
     DevBuf<PgoOut> d_out;
+    int solver = NDT_PGO_SOLVER_CG;
+    DevBuf<double> d_dir, d_S;              // the direct solve: Kw and C; the dense matrix (grows, never shrinks)
+    DevBuf<PgoDirectState> d_st;
+    ndt_pgo_solver_stats_t stats{};          // of the last optimise
     std::vector<ndt_pgo_record> hist;       // of the last optimise
     std::vector<double> weights;            // of the last optimise (between factors)
     std::vector<double> pweights;           // of the last optimise (position factors)
@@ -45,7 +52,75 @@ static bool pgo_valid_params(const ndt_pgo_params* p) {
     return true;
 }
 
+// The direct solve's outer iterations on the ctx stream (the inputs are already uploaded): the linearisation at the input,
+// then per iteration the Schur build, the factorisation with b carried along, the back substitution and the step fused
+// with the next linearisation; the status block is read after each and decides whether another is enqueued.
+static ndt_status pgo_run_direct(ndt_pgo* g, const PgoGraph& d, const PgoArgs& a, PgoOut* o) {
+    ndt_ctx* c = g->c;
+    hipStream_t st = c->stream.get();
+    const size_t n = (size_t)d.n, dim = 6 * (size_t)d.m + 3 * (size_t)d.np;
+    PgoDirect dg;
+    dg.d = (int)dim;
+    dg.dp = (int)((dim + kPgoDirectTile - 1) / kPgoDirectTile) * kPgoDirectTile;
+    TRY(ensure(c, g->d_dir, 6 * dim + 36 * n));
+    TRY(ensure(c, g->d_S, ((size_t)dg.dp + 1) * (size_t)dg.dp));
+    TRY(ensure(c, g->d_st, 1));
+    dg.kw = g->d_dir.p;
+    dg.C = dg.kw + 6 * dim;
+    dg.S = g->d_S.p;
+    dg.st = g->d_st.p;
+    HIPCHK(c, hipMemsetAsync(dg.st, 0, sizeof(PgoDirectState), st));
+    const int nt = dg.dp / kPgoDirectTile, nfb = (d.m + d.np + 15) / 16;
+    PgoDirectState h;
+    int factorizations = 0;
+    for (int first = 1;; first = 0) {
+        hipLaunchKernelGGL(k_pgo_direct_step, dim3(1), dim3(kPgoBlock), 0, st, d, a, dg, first);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&h, dg.st, sizeof h, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (h.done) break;
+        if (dg.d == 0) continue;
+        hipLaunchKernelGGL(k_pgo_schur, dim3(nfb, nfb), dim3(256), 0, st, d, dg);
+        for (int kt = 0; kt < nt; ++kt) {
+            hipLaunchKernelGGL(k_pgo_chol_diag, dim3(1), dim3(256), 0, st, dg, kt);
+            hipLaunchKernelGGL(k_pgo_chol_panel, dim3(nt - kt), dim3(256), 0, st, dg, kt);
+            if (kt + 1 < nt) hipLaunchKernelGGL(k_pgo_chol_trail, dim3(nt - kt - 1, nt - kt), dim3(256), 0, st, dg, kt);
+        }
+        hipLaunchKernelGGL(k_pgo_chol_back, dim3(1), dim3(256), 0, st, dg);
+        HIPCHK(c, hipGetLastError());
+        ++factorizations;
+    }
+    // as under CG: set once the launches ran, whatever status they report; a HIP error leaves the earlier optimise's
+    g->stats = ndt_pgo_solver_stats_t{NDT_PGO_SOLVER_DIRECT, dg.d, kPgoDirectTile, factorizations, 0};
+    o->status = h.status;
+    o->bad = h.bad;
+    o->iterations = h.iterations;
+    o->converged = h.converged;
+    o->cg_iterations = 0;
+    o->cost0 = h.cost0;
+    o->cost = h.cost;
+    o->max_step = h.max_step;
+    return NDT_OK;
+}
+
 extern "C" {
+
+ndt_status ndt_pgo_set_solver(ndt_pgo* g, int solver) {
+    if (!g) return NDT_EINVAL;
+    if (solver != NDT_PGO_SOLVER_CG && solver != NDT_PGO_SOLVER_DIRECT)
+        return fail(g->c, NDT_EINVAL, "unknown pose-graph solver " + std::to_string(solver) + " (0: CG, 1: direct)");
+    g->solver = solver;
+    return NDT_OK;
+}
+
+int ndt_pgo_get_solver(const ndt_pgo* g) { return g ? g->solver : -1; }
+
+ndt_status ndt_pgo_solver_stats(ndt_pgo* g, ndt_pgo_solver_stats_t* out) {
+    if (!g) return NDT_EINVAL;
+    if (!out) return fail(g->c, NDT_EINVAL, "null argument");
+    *out = g->stats;
+    return NDT_OK;
+}
 
 // pgo_node's constants (pgo_node.cpp:85-93: prior 1e-12 x 6, odometry 1e-6 x 3 (rotation), 1e-4 x 3 (translation)).
 // step_eps 1e-10 (rad, m) and cg_rtol 1e-10 are this library's: the reweighted iteration converges linearly, so the
@@ -158,6 +233,11 @@ ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
     const size_t n = (size_t)ndt_pgo_size(g), m = g->li.size(), np = g->pnode.size();
     if (n == 0) return fail(c, NDT_EINVAL, "the pose graph has no node");
     if (m > 0x3fffffffULL / 36 || n > 0x3fffffffULL / 18 || np > 0x3fffffffULL / 14) return fail(c, NDT_EINVAL, "pose graph too large");
+    const bool direct = g->solver == NDT_PGO_SOLVER_DIRECT;
+    const size_t dim = 6 * m + 3 * np;
+    if (direct && dim > (size_t)kPgoDirectMaxDim)
+        return fail(c, NDT_EINVAL, "direct solve: d = 6 m + 3 np = " + std::to_string(dim) + " is over the limit of " +
+                                       std::to_string(kPgoDirectMaxDim) + "; the estimate is unchanged");
     TRY(set_dev(c));
     // per-node lists of loop edges (2 * edge + side), edges in insertion order; the position factors' slots by node
     std::vector<int> ints(2 * m + n + 1 + 2 * m + n + 1 + np, 0);
@@ -256,11 +336,16 @@ ndt_status ndt_pgo_optimize(ndt_pgo* g, ndt_pgo_result* out) {
         a.sig_prior[i] = std::sqrt(g->prm.prior_var[i]);
         a.sig_odom[i] = std::sqrt(g->prm.odom_var[i]);
     }
-    hipLaunchKernelGGL(k_pgo_optimize, dim3(1), dim3(kPgoBlock), 0, c->stream.get(), d, a);
-    HIPCHK(c, hipGetLastError());
     PgoOut o;
-    HIPCHK(c, hipMemcpyAsync(&o, g->d_out.p, sizeof o, hipMemcpyDeviceToHost, c->stream.get()));
-    HIPCHK(c, hipStreamSynchronize(c->stream.get()));
+    if (direct) {
+        TRY(pgo_run_direct(g, d, a, &o));
+    } else {
+        hipLaunchKernelGGL(k_pgo_optimize, dim3(1), dim3(kPgoBlock), 0, c->stream.get(), d, a);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&o, g->d_out.p, sizeof o, hipMemcpyDeviceToHost, c->stream.get()));
+        HIPCHK(c, hipStreamSynchronize(c->stream.get()));
+        g->stats = ndt_pgo_solver_stats_t{NDT_PGO_SOLVER_CG, (int)std::min<size_t>(dim, 0x7fffffff), 0, 0, 0};
+    }
     if (o.status == kPgoNearPi) {
         const std::string what = o.bad == 0 ? "the prior" : o.bad < (int)n ? "odometry edge " + std::to_string(o.bad - 1) + " -> " + std::to_string(o.bad)
                                                                             : "between factor " + std::to_string(o.bad - (int)n);

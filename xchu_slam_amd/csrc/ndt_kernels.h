@@ -67,6 +67,12 @@ __global__ void k_isc_finalize(const unsigned*, IscDb, int, int, int, double, do
 __global__ void k_isc_detect(IscDb, const int*, int, IscDetectArgs, IscPartial*);
 __global__ void k_isc_reduce(const IscPartial*, const int*, int, int, IscDetectArgs, ndt_isc_result*);
 __global__ void k_pgo_optimize(PgoGraph, PgoArgs);
+__global__ void k_pgo_direct_step(PgoGraph, PgoArgs, PgoDirect, int);
+__global__ void k_pgo_schur(PgoGraph, PgoDirect);
+__global__ void k_pgo_chol_diag(PgoDirect, int);
+__global__ void k_pgo_chol_panel(PgoDirect, int);
+__global__ void k_pgo_chol_trail(PgoDirect, int);
+__global__ void k_pgo_chol_back(PgoDirect);
 __global__ void k_map_stack(const float4*, const int*, const long long*, const Mat4f*, int, int, int, float4*);
 __global__ void k_fit_block_flags(const int*, const GridHeader*, int*);
 __global__ void k_append2(const float4*, const float4*, int, const GridHeader*, float4*, float4*);

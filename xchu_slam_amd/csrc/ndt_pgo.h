@@ -72,6 +72,27 @@ struct PgoArgs {
     double sig_prior[6], sig_odom[6];   // standard deviations
 };
 
+// The direct loop-space solve (posegraph_direct.hip).  d = 6 m + 3 np rows of B: between factor q owns rows 6 q .. 6 q + 5,
+// the position factor in slot q rows 6 m + 3 q .. + 2.  S is dp x dp (d rounded up to whole tiles, the padding an identity),
+// lower triangle, row-major with leading dimension dp; row dp carries b, then the forward solve, then z = S^-1 b.
+struct PgoDirectState {
+    int status;         // PgoStatus
+    int bad;            // kPgoNearPi: the factor, as PgoOut's
+    int iterations;
+    int converged;
+    int done;           // the host enqueues no further iteration
+    int pivot_bad;      // a pivot of the factorisation was not finite or below kPgoPivotMin
+    double cost0, cost, max_step;
+};
+
+struct PgoDirect {
+    int d, dp;
+    double* kw;           // [d][6]  one row of Kw per row of B
+    double* C;            // [n][36] prefix sums of P_t P_t^T
+    double* S;            // [dp + 1][dp]
+    PgoDirectState* st;
+};
+
 // ------------------------------------------------------------------------------------------------ 3 x 3 helpers
 __host__ __device__ inline void m3_mul(const double* A, const double* B, double* C) {  // C = A B
     for (int i = 0; i < 3; ++i)

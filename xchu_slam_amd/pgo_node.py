@@ -118,7 +118,7 @@ class PGO(_CtxObject):
     min_keyframes: no detection below that many keyframes (:300).  max_pair_dist: the planar gate of methods 1 and 2 on
     the corrected poses (method 0 accepts below 30 m, :335).  robust_k: the Cauchy width of loop and GPS factors.
     literal_measurement: loop_measurement's.  detect_args: the detector's parameters (ScParams / IscParams fields);
-    pgo_args: PoseGraph's.  detect_every: detection runs on every detect_every-th keyframe.
+    pgo_args: PoseGraph's; solver: PoseGraph's ("cg" or "direct"; a "solver" entry of pgo_args, if there is one, wins).  detect_every: detection runs on every detect_every-th keyframe.
     append: "predict" keeps the solve off keyframes that add no information (a node that brings only its odometry edge
     gets the estimate X_{k-1} (P_{k-1}^-1 P_k), no launch; while the graph holds no loop or position factor `poses` is the
     odometry bit for bit); "optimize" solves after every keyframe, the reference's sequence of ISAM2Update calls.
@@ -133,7 +133,7 @@ class PGO(_CtxObject):
                  search_num: int = 25, score_threshold: float = 0.3, method: str = "icp", robust_k: float = 1.0,
                  literal_measurement: bool = False, literal_root: bool = False, detect_args: dict | None = None,
                  pgo_args: dict | None = None, append: str = "predict", detect_every: int = 1,
-                 literal_reject_stops: bool = False):
+                 literal_reject_stops: bool = False, solver="cg"):
         if loop_method not in (0, 1, 2):
             raise ValueError("loop_method is 0 (radius search), 1 (Scan Context) or 2 (Intensity Scan Context)")
         if append not in ("predict", "optimize"):
@@ -159,7 +159,7 @@ class PGO(_CtxObject):
                 self._detector = SCManager(registration=self._reg, **dict({"dist_thres": 0.2}, **args))
             elif loop_method == 2:
                 self._detector = ISCGeneration(registration=self._reg, **dict({"rings": 60, "sectors": 60, "max_dis": 40.0}, **args))
-            self._graph = PoseGraph(registration=self._reg, **(pgo_args or {}))
+            self._graph = PoseGraph(registration=self._reg, **dict({"solver": solver}, **(pgo_args or {})))
         except Exception:
             self.close()
             raise
@@ -382,7 +382,7 @@ def run_mapping(scans, stamps, directory=None, odom_args: dict | None = None, fi
     """The three nodes offline (the reference README's "offline version"): each scan ((N, 4) x,y,z,intensity) goes
     through filter_scan (filter_node), LidarOdom.process (odom_node) and PGO.push (pgo_node) with the filtered cloud and
     the odometry's current_pose; with a directory, SaveMap's files are written at the end (lidar_odom.txt included).
-    odom_args: LidarOdom's parameters; filter_args: filter_scan's; **pgo_args: PGO's.
+    odom_args: LidarOdom's parameters; filter_args: filter_scan's; **pgo_args: PGO's (solver= among them).
 
     Returns the back end's state and the per-scan odometry: keyframes (the scan index of every keyframe), odom_poses,
     poses, times, loops, rejected, log, odometry ((N, 6) current_pose per scan), stamps, optimize_launches,

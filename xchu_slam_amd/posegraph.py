@@ -24,12 +24,14 @@ import numpy as np
 
 from . import synth
 from ._ctxobj import _CtxObject
-from ._lib import PgoParams, PgoRecord, PgoResult, check
+from ._lib import PGO_SOLVER_CG, PGO_SOLVER_DIRECT, PgoParams, PgoRecord, PgoResult, PgoSolverStats, check
 from .ndt import NormalDistributionsTransform, _dp
 
 __all__ = ["PoseGraph", "gps_factors", "loop_measurement", "optimize_loops"]
 
 _PARAM_NAMES = tuple(k for k, _ in PgoParams._fields_)
+_SOLVERS = {"cg": PGO_SOLVER_CG, "direct": PGO_SOLVER_DIRECT}
+_SOLVER_NAMES = {v: k for k, v in _SOLVERS.items()}
 
 
 def _pose44(pose) -> np.ndarray:
@@ -55,12 +57,14 @@ def _inv(T: np.ndarray) -> np.ndarray:
 class PoseGraph(_CtxObject):
     """The pose graph of pgo_node on MI355X.  It runs on a registration context: its own, or the one of an existing
     NormalDistributionsTransform (`registration=`), whose device and stream it then shares.  **params are
-    ndt_pgo_params fields: max_iter, step_eps, cg_max_iter, cg_rtol, prior_var, odom_var."""
+    ndt_pgo_params fields: max_iter, step_eps, cg_max_iter, cg_rtol, prior_var, odom_var.  solver: the linear solver
+    of each Gauss-Newton step, "cg" (conjugate gradients inside one launch, the default) or "direct" (the dense loop-space
+    factorisation of csrc/posegraph_direct.hip; at most 6 loops + 3 positions = 8192 rows)."""
 
     _DESTROY = "ndt_pgo_destroy"
     _WHAT = "pose-graph"
 
-    def __init__(self, device: int = 0, registration: NormalDistributionsTransform | None = None, **params):
+    def __init__(self, device: int = 0, registration: NormalDistributionsTransform | None = None, solver="cg", **params):
         super().__init__(device, registration)
 
         def six(k, v):  # a variance: one value for all six components, or six
@@ -70,6 +74,32 @@ class PoseGraph(_CtxObject):
         pg = C.c_void_p()
         check(self._lib.ndt_pgo_create(self.ctx, C.byref(self._params), C.byref(pg)), self.ctx)
         self._handle = pg
+        if solver != "cg":
+            try:
+                self.set_solver(solver)
+            except Exception:
+                self.close()
+                raise
+
+    def set_solver(self, solver):
+        """The linear solver of later optimize() calls: "cg" or "direct" (or the C ABI's NDT_PGO_SOLVER_* value)."""
+        if isinstance(solver, str):
+            if solver not in _SOLVERS:
+                raise ValueError("solver is 'cg' or 'direct'")
+            solver = _SOLVERS[solver]
+        check(self._lib.ndt_pgo_set_solver(self._handle, int(solver)), self.ctx)
+
+    @property
+    def solver(self) -> str:
+        return _SOLVER_NAMES[int(self._lib.ndt_pgo_get_solver(self._handle))]
+
+    def solver_stats(self) -> dict:
+        """Of the last optimize(): the solver it used, d = 6 loops + 3 positions, and under "direct" the tile width, the
+        number of factorisations and whether a refinement pass ran."""
+        st = PgoSolverStats()
+        check(self._lib.ndt_pgo_solver_stats(self._handle, C.byref(st)), self.ctx)
+        return {"solver": _SOLVER_NAMES[int(st.solver)], "d": int(st.d), "tile": int(st.tile),
+                "factorizations": int(st.factorizations), "refined": bool(st.refined)}
 
     def __len__(self) -> int:
         return int(self._lib.ndt_pgo_size(self._handle))
@@ -217,13 +247,13 @@ def gps_factors(keyframe_times, poses, gps_times, altitudes, eps: float = 0.1, a
 
 
 def optimize_loops(poses, accepted, literal_measurement: bool = False, robust_k: float = 1.0, device: int = 0, registration=None,
-                   positions=None, **params):
+                   positions=None, solver="cg", **params):
     """pgo_node's back end for a replay: the graph of `poses` (per keyframe a 4 x 4 or (x, y, z, roll, pitch, yaw)) and
     of `accepted` as close_loops returns it ([(loop_idx, curr_idx, transform, score)]; the score is the loop factor's
     variance, as pgo_node.cpp:453-457 has it) and of `positions` ([(node, xyz, var)] as gps_factors returns it, each a
-    position factor with robust_k), one optimise.  Returns (poses6d (n, 6), info); info is optimize()'s dict plus
+    position factor with robust_k), one optimise with PoseGraph's `solver`.  Returns (poses6d (n, 6), info); info is optimize()'s dict plus
     "weights", "position_weights" and "poses" (n, 4, 4)."""
-    with PoseGraph(device, registration, **params) as pg:
+    with PoseGraph(device, registration, solver=solver, **params) as pg:
         for p in poses:
             pg.add_node(p)
         for loop_idx, curr_idx, T, score in accepted:
